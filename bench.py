@@ -3,6 +3,14 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
                     [--mode frames|rows] [--frames F]
+                    [--dump-outputs DIR] [--full]
+
+A plain run uploads the frames, warms up, times exactly --steps steps and
+prints the result line (`ms_per_step`: the milliseconds one timed step took).
+--dump-outputs DIR then writes what the last timed step returned to its
+caller on rank 0 (dump_outputs below).  Everything else described here -- the
+check against the golden fixtures ("verified"), the roofline region, the
+detail.* legs and `cpu_baseline` -- runs only with --full.
 
 Workload (BASELINE.json metric "Mpixels/sec DivQuant K=256 on 4K RGB"):
 
@@ -11,8 +19,8 @@ Workload (BASELINE.json metric "Mpixels/sec DivQuant K=256 on 4K RGB"):
   frames this rank owns, already resident in HBM, in ONE batched call.
   Default F = 8: C4's per-GPU share (C4 = 64 4K frames over 8 GPUs, so
   --gpus 8 is exactly C4).  Frames are independent objects: no data-path
-  collective, "scaling": "weak".  The same run also measures, each verified
-  against the reference build's outputs:
+  collective, "scaling": "weak".  With --full the same run also measures,
+  each verified against the reference build's outputs:
     detail.c3         C3: one 4K frame per call;
     detail.c2         C2: one 1920x1080 frame per call, K=256;
     detail.c5         C5: the 16384x16384 K=1024 tile, its rows split over the
@@ -34,11 +42,11 @@ Workload (BASELINE.json metric "Mpixels/sec DivQuant K=256 on 4K RGB"):
 (torch.distributed.run, one process per GPU, RCCL over xGMI) before any GPU
 call in this process; every rank asserts the world size is N.
 
-Frames are the SURVEY 8c/8d generator (xorshift64, frame f = seed + f); the
-outputs of the timed work are checked against the reference build's golden
-fixtures (tests/golden/c4.json, big.json) after the timed region and the run
-FAILS on a mismatch ("verified" fields).  Prints ONE JSON line on rank 0.
-`roofline` is the kernel with the largest measured time in the step, timed
+Frames are the SURVEY 8c/8d generator (xorshift64, frame f = seed + f: the
+same inputs in every run); with --full the outputs of the timed work are
+checked against the reference build's golden fixtures (tests/golden/c4.json,
+big.json) after the timed region and the run FAILS on a mismatch ("verified"
+fields).  Prints ONE JSON line on rank 0.  With --full, `roofline` is the kernel with the largest measured time in the step, timed
 live on the library's stream with HIP events around every launch, against
 the 8 TB/s HBM peak, with its bytes from the engine work model
 and SURVEY 8(d)'s model beside it; `traffic` comes from the committed
@@ -106,6 +114,11 @@ def parse(argv=None):
     ap.add_argument("--mode", default="frames", choices=["frames", "rows"])
     ap.add_argument("--frames", type=int, default=None,
                     help="frames per rank per step (frames mode, default 8) / frames per step (rows, default 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the golden-fixture check, the "
+                         "roofline region, the detail legs and the CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-timing", action="store_true", help="skip the HIP-event roofline region")
     ap.add_argument("--no-c3", action="store_true", help="skip the single-frame C3 measurement")
@@ -509,6 +522,29 @@ def copy_rate_gbs(torch, dev, mib=1024, reps=10):
     return 2.0 * (mib << 20) / (ms / 1e3) / 1e9
 
 
+DUMP_VALUES = 4 << 20   # float64 values --dump-outputs writes at most for the label maps (32 MB)
+
+
+def dump_outputs(directory, outs, cts):
+    """--dump-outputs: what the last timed step handed its caller on rank 0,
+    as float64 (exact for the u32 colours): colortable_fNN.npy, frame NN's
+    colortable, and out_fNN.npy, its mapped pixels -- all of them, or, where
+    the frames together exceed DUMP_VALUES, the pixels at a fixed seeded
+    sample of positions (ascending, the same in every run and for every
+    frame of one size)."""
+    os.makedirs(directory, exist_ok=True)
+    per = max(1, DUMP_VALUES // max(1, len(outs)))
+    picks = {}
+    for i, (o, ct) in enumerate(zip(outs, cts)):
+        px = o.cpu().numpy().view(np.uint32)
+        if px.size > per:
+            if px.size not in picks:
+                picks[px.size] = np.unique(np.random.default_rng(20240607).integers(0, px.size, per))
+            px = px[picks[px.size]]
+        np.save(os.path.join(directory, "out_f%02d.npy" % i), px.astype(np.float64))
+        np.save(os.path.join(directory, "colortable_f%02d.npy" % i), np.asarray(ct, np.uint32).astype(np.float64))
+
+
 def upload_frames(torch, pkg, dev, w, h, ids, rows=None):
     """Synthetic frames `ids` on the device (whole, or rows [r0, r1) of each)."""
     ts = []
@@ -626,7 +662,7 @@ def main():
     sync = lambda: torch.cuda.synchronize(dev)  # noqa: E731
     ctx = {"torch": torch, "pkg": pkg, "dev": dev, "local": local, "rank": rank, "world": world,
            "stream": stream, "sync": sync, "nf": a.frames}
-    verify = not a.no_verify
+    verify = a.full and not a.no_verify
 
     w, h, k = CONFIGS[a.config]
     n = w * h
@@ -676,6 +712,8 @@ def main():
     # --- timed region: no per-launch events (they would perturb the timing)
     pkg.set_timing(False, device=local)
     dt = timed_region(step, a.steps, world, sync)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outs, last["cts"])
     # --- correctness of the timed work: the last step's outputs vs the reference
     verified = None
     if verify:
@@ -698,7 +736,7 @@ def main():
     # --- roofline region: the same steps again with HIP events around every
     # launch (on the library's launch stream) for per-kernel durations
     stats = {}
-    if not a.no_timing:
+    if a.full and not a.no_timing:
         # kernels measured un-overlapped: one engine lane, so an event pair
         # around a launch times that kernel alone on the GPU
         pkg.set_lanes(1)
@@ -718,7 +756,7 @@ def main():
     value = px_per_step * a.steps / dt / 1e6
 
     detail = {}
-    big4k = a.mode == "frames" and (w, h, k) == (3840, 2160, 256)
+    big4k = a.full and a.mode == "frames" and (w, h, k) == (3840, 2160, 256)
     # --- C3: one 4K frame per call (this rank's first frame)
     if big4k and not a.no_c3 and nf > 1:
         dt1, ok1 = frame_leg(ctx, "c3", a.steps, verify)
@@ -727,7 +765,7 @@ def main():
                         "workload": "one 3840x2160 frame per call (C3), K=256, %d rank(s)" % world,
                         "verified": ok1}
     # --- C2: one 1920x1080 frame per call, K=256
-    if a.mode == "frames" and not a.no_c2:
+    if a.full and a.mode == "frames" and not a.no_c2:
         w2, h2, _ = CONFIGS["c2"]
         dt2, ok2 = frame_leg(ctx, "c2", a.steps, verify)
         detail["c2"] = {"ms_per_frame": round(dt2 * 1e3 / a.steps, 3),
@@ -822,7 +860,7 @@ def main():
         del frames, outs
         torch.cuda.empty_cache()
     # --- C5: the gigapixel tile, rows over the ranks (N=1: whole on one GPU)
-    if a.mode == "frames" and not a.no_c5:
+    if a.full and a.mode == "frames" and not a.no_c5:
         w5, h5, k5 = CONFIGS["c5"]
         s5 = max(1, min(5, a.steps))
         dt5, ok5, comm5 = rows_leg(ctx, "c5", 1, s5, 2, verify)
@@ -874,6 +912,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": round(dt * 1e3 / a.steps, 3),
             "higher_is_better": True,
             "scaling": scaling,
@@ -890,7 +929,7 @@ def main():
             "roofline": roof,
             "detail": detail,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(3840, 2160, 256)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -96,6 +96,44 @@ def test_row_ranges_partition_the_frame():
             assert max(sizes) - min(sizes) <= 1
 
 
+def test_bench_plain_and_full_options():
+    """A plain run asks for nothing beyond the timed steps; --full and
+    --dump-outputs are options of their own."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 copies of each frame's colortable and mapped
+    pixels -- whole frames while they fit, else the same seeded sample of
+    positions in every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    px = [rng.integers(0, 1 << 24, 5000, dtype=np.uint32) for _ in range(3)]
+    outs = [torch.from_numpy(p.view(np.int32)) for p in px]
+    cts = [np.arange(4 + i, dtype=np.uint32) * 0x010203 for i in range(3)]
+    bench.dump_outputs(str(tmp_path / "a"), outs, cts)
+    for i in range(3):
+        o = np.load(tmp_path / "a" / ("out_f%02d.npy" % i))
+        c = np.load(tmp_path / "a" / ("colortable_f%02d.npy" % i))
+        assert o.dtype == np.float64 and np.array_equal(o, px[i])
+        assert c.dtype == np.float64 and np.array_equal(c, cts[i])
+    monkeypatch.setattr(bench, "DUMP_VALUES", 3 * 1000)
+    bench.dump_outputs(str(tmp_path / "b"), outs, cts)
+    bench.dump_outputs(str(tmp_path / "c"), outs, cts)
+    for i in range(3):
+        o = np.load(tmp_path / "b" / ("out_f%02d.npy" % i))
+        assert 900 < o.size <= 1000 and np.isin(o, px[i]).all()
+        assert np.array_equal(o, np.load(tmp_path / "c" / ("out_f%02d.npy" % i)))
+
+
 def test_bench_gpus_2_launches_two_ranks():
     """`bench.py --gpus 2` with no torchrun environment starts two ranks by
     itself (torch.distributed.run; gloo on CPU, RCCL on the GPU box), every

@@ -10,7 +10,7 @@ ROUNDS=$2
 shift 2
 mkdir -p $O
 cd $R
-B="bench.py --no-c3 --no-c2 --no-c5 --no-bgr --no-cpu-baseline --no-timing"
+B="bench.py --full --no-c3 --no-c2 --no-c5 --no-bgr --no-cpu-baseline --no-timing"
 K='import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); r=d["detail"].get("c4_rowtile",{}); print(d["ms_per_step"], d["verified"]["ok"], r.get("ms_per_step"), r.get("verified"), round(r.get("ms_per_step",0)/8/d["ms_per_step"],3))'
 for i in $(seq 1 $ROUNDS); do
   for L in "$@"; do

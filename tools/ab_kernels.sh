@@ -11,7 +11,7 @@ ROUNDS=$2
 shift 2
 mkdir -p $O
 cd $R
-B="bench.py --lanes 1 --no-c3 --no-c2 --no-c5 --no-rowtile --no-bgr --no-cpu-baseline --steps 20 --warmup 5"
+B="bench.py --full --lanes 1 --no-c3 --no-c2 --no-c5 --no-rowtile --no-bgr --no-cpu-baseline --steps 20 --warmup 5"
 K='import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); print(d["ms_per_step"], d["verified"]["ok"], {k:(v["launches"],round(v["ms"]*1e3/v["launches"],1)) for k,v in d["detail"]["kernels"].items()})'
 for i in $(seq 1 $ROUNDS); do
   for L in "$@"; do

@@ -17,6 +17,6 @@ tail -1 $O/smoke.txt
 DQ_HIP_TRACE=1 timeout -k 10 300 rocprofv3 --kernel-trace -f csv -d $O/c3prof -o run -- python3 -u tools/c3_trace.py 20 > $O/c3_calls.txt 2> $O/c3_host_trace.txt || { tail -5 $O/c3_host_trace.txt; exit 1; }
 python3 tools/timeline.py $O/c3prof 130 > $O/timeline_c3.txt
 tail -1 $O/c3_calls.txt
-timeout -k 10 900 python3 -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 900 python3 -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 tail -c 600 $O/bench_default.json
 echo final done

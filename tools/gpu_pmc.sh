@@ -9,7 +9,7 @@ O=$R/gpurun_out/$1
 shift
 mkdir -p $O
 cd $R
-B="bench.py --lanes 1 --no-c3 --no-c2 --no-c5 --no-rowtile --no-bgr --no-cpu-baseline --no-timing --steps 2 --warmup 1"
+B="bench.py --full --lanes 1 --no-c3 --no-c2 --no-c5 --no-rowtile --no-bgr --no-cpu-baseline --no-timing --steps 2 --warmup 1"
 i=0
 for G in "$@"; do
   i=$((i + 1))

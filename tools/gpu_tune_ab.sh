@@ -12,7 +12,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread > $O/pytest_gpu.txt 2>&1 || { tail -30 $O/pytest_gpu.txt; exit 1; }
 tail -1 $O/pytest_gpu.txt
-B="bench.py --no-c3 --no-c2 --no-bgr --no-weighted --no-cpu-baseline --no-timing"
+B="bench.py --full --no-c3 --no-c2 --no-bgr --no-weighted --no-cpu-baseline --no-timing"
 K='import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); t=d["detail"]; r=t.get("c4_rowtile",{}); c=t.get("c5",{}); print("share", d["ms_per_step"], d["verified"]["ok"], "c5", c.get("ms_per_tile"), c.get("verified"), "rowtile", r.get("ms_per_step"), r.get("verified"))'
 for i in $(seq 1 $ROUNDS); do
   for t in tree "$@"; do

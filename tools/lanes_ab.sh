@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
-B="bench.py --no-c3 --no-c2 --no-c5 --no-rowtile --no-bgr --no-weighted --no-timing --no-cpu-baseline --steps 20 --warmup 10"
+B="bench.py --full --no-c3 --no-c2 --no-c5 --no-rowtile --no-bgr --no-weighted --no-timing --no-cpu-baseline --steps 20 --warmup 10"
 for i in $(seq 1 $2); do
   for cfg in 8:4 12:4 12:5 12:6 16:8; do
     q=${cfg%%:*}; l=${cfg##*:}

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
-B="bench.py --no-c2 --no-c5 --no-rowtile --no-bgr --no-weighted --no-timing --no-cpu-baseline --steps 30 --warmup 10"
+B="bench.py --full --no-c2 --no-c5 --no-rowtile --no-bgr --no-weighted --no-timing --no-cpu-baseline --steps 30 --warmup 10"
 for i in $(seq 1 $2); do
   for q in 8 12; do
     DQ_BENCH_HW_QUEUES=$q timeout -k 10 200 python3 -u $B > $O/q${q}_$i.json 2> $O/q${q}_$i.err
