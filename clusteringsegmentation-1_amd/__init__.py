@@ -94,6 +94,7 @@ def lib():
         "dq_hip_last_loop_rounds": ([c.c_int], c.c_int),
         "dq_hip_set_persist": ([c.c_int, c.c_int], None),
         "dq_hip_set_wsmall": ([c.c_int, c.c_int], None),
+        "dq_hip_set_lds_map": ([c.c_int, c.c_int], None),
         "dq_hip_last_wsmall_profile": ([c.c_int, c.c_void_p, c.c_int], c.c_int),
         "dq_hip_last_persist_rounds": ([c.c_int], c.c_int),
         "dq_hip_set_timing": ([c.c_int, c.c_int], None),
@@ -651,6 +652,12 @@ def set_persist(on, device=0):
 def set_wsmall(on, device=0):
     """The one-launch weighted path for small inputs on / off (every lane)."""
     lib().dq_hip_set_wsmall(device, 1 if on else 0)
+
+
+def set_lds_map(on, device=0):
+    """map_lds_kernel for palettes of at most 1024 entries on / off (every
+    lane); off: map_kernel, as for larger palettes (identical outputs)."""
+    lib().dq_hip_set_lds_map(device, 1 if on else 0)
 
 
 def last_wsmall_profile(device=0):

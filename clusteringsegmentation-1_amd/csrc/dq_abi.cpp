@@ -925,6 +925,10 @@ void dq_hip_set_wsmall(int device, int on) {
   for (int l = 0; l < dq::kMaxLanes; ++l) engine_for(device, l).set_wsmall(on != 0);
 }
 
+void dq_hip_set_lds_map(int device, int on) {
+  for (int l = 0; l < dq::kMaxLanes; ++l) engine_for(device, l).set_lds_map(on != 0);
+}
+
 void dq_hip_set_timing(int device, int on) { engine_for(device).set_timing(on != 0); }
 
 void dq_hip_set_debug(int device, int flags) {

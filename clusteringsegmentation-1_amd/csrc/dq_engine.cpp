@@ -2583,6 +2583,7 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
       const MapTask* dt = reinterpret_cast<const MapTask*>(d_mapstage_);
       timed_begin(stream);
       launch_build_cells(dt, nbuild, kmax, stream);
+      DQ_HIP(hipGetLastError());   // (a rejected launch would leave the output as it was)
       timed_end(ST_CELLS, 0.0, stream);
       // (the staging-reuse event behind the map's kernels, as for round tables)
       double px = 0, mb = 0;   // pixels; bytes: 4 (BGR24: 3) read + 4 written per pixel
@@ -2593,6 +2594,7 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
       timed_begin(stream);
       if (lds_map) launch_map_lds(dt, nt, kmax, nblocks, ht[0].bgr != 0, stream);
       else launch_map(dt, nt, kmax, nblocks, stream);
+      DQ_HIP(hipGetLastError());
       timed_end(ST_MAP, mb, stream, px);
       DQ_HIP(hipEventRecord(map_ev_, stream));
       map_pending_ = true;
@@ -2625,9 +2627,11 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
         const uint32_t nb = std::max<uint32_t>(1, (j.n / 8 + one.grp_per_block - 1) / one.grp_per_block);
         timed_begin(stream);
         launch_build_cells(dt, 1, j.k, stream);
+        DQ_HIP(hipGetLastError());
         timed_end(ST_CELLS, 0.0, stream);
         timed_begin(stream);
         launch_map(dt, 1, j.k, nb, stream);
+        DQ_HIP(hipGetLastError());
         timed_end(ST_MAP, 8.0 * (double)j.n, stream, (double)j.n);
         if (st)
           DQ_HIP(hipMemcpyAsync(j.d_out, d_map_align_ + want, (size_t)j.n * 4, hipMemcpyDeviceToDevice, stream));

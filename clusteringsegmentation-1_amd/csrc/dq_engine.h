@@ -268,6 +268,7 @@ class Engine {
   void set_persist(bool on) { persist_ = on; }
   // the one-workgroup weighted path for small inputs (launch_wsmall; default on)
   void set_wsmall(bool on) { wsmall_ = on; }
+  void set_lds_map(bool on) { use_lds_map_ = on; }
   bool plan() const { return plan_; }
   bool fixed_point() const { return fixed_point_; }
   void reset_stats();

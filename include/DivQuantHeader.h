@@ -70,7 +70,8 @@ long timediff(clock_t t1, clock_t t2);
 void map_colors_mps ( const uint32_t *inPixelsPtr, uint32_t numPixels, uint32_t *outPixelsPtr, uint32_t *outColortablePtr, int colormapSize );
 
 /* DivQuantMapColors.cpp:82-203 -- unique colours + normalised counts
- * (hash-bucket order).  Host utility; returns new[]-allocated weights. */
+ * (hash-bucket order), host pointers in and out.  GPU: the weighted path's
+ * colour table on the MI355X.  Returns new[]-allocated weights. */
 double *
 calc_color_table ( const uint32_t *inPixels,
                   const uint32_t numPixels,

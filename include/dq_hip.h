@@ -267,6 +267,12 @@ int dq_hip_last_persist_rounds(int device);
  * sequential folds, dedup and, for at most 16 deduped colours, the map.
  * Outputs are identical either way. */
 void dq_hip_set_wsmall(int device, int on);
+/* The map kernel of palettes of at most 1024 entries: on (the default;
+ * DQ_HIP_TUNE=lds_map=0 turns the default off) -- map_lds_kernel, the compact
+ * cell table in LDS; off -- map_kernel, the cell records gathered through L2,
+ * which every larger palette and every misaligned buffer takes anyway.
+ * Every lane of the device.  Outputs are identical either way. */
+void dq_hip_set_lds_map(int device, int on);
 /* Phase profile of the last weighted call if it took the one-launch path
  * (0 values otherwise): wall_clock64 ticks (100 MHz) at its start, hash set,
  * sorted colour table, clustering, map; ticks in fold passes and partitions;

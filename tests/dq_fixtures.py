@@ -184,7 +184,100 @@ def make_palette(spec):
         return subdivided_colors()
     if kind == "gray":
         return (((r[:k] & 0xFF)) * 0x010101).astype(np.uint32)
+    if kind == "lattice":            # every multiple of `step` per channel: midpoints tie 2-, 4-, 8-way
+        v = np.arange(0, 256, spec["step"], dtype=np.uint32)
+        assert len(v) ** 3 == k
+        return ((v[:, None, None] << 16) | (v[None, :, None] << 8) | v[None, None, :]).reshape(-1)
+    if kind == "cube":               # side^3 entries of step 2 from 100: a few cells hold them all
+        v = (100 + 2 * np.arange(spec["side"])).astype(np.uint32)
+        assert len(v) ** 3 == k and v[-1] < 256
+        return ((v[:, None, None] << 16) | (v[None, :, None] << 8) | v[None, None, :]).reshape(-1)
+    if kind == "cluster":            # k distinct colours of ONE 8x8x8 cell: that cell has exactly k candidates
+        assert k <= 512
+        q = xorshift(3 + 512, seed=SEED + 1 + spec["seed"])
+        o = np.argsort(q[3:], kind="stable")[:k].astype(np.uint32)
+        c = (q[:3] % 32) * 8
+        return (((c[0] + (o >> 6)) << 16) | ((c[1] + ((o >> 3) & 7)) << 8) | (c[2] + (o & 7))).astype(np.uint32)
     raise ValueError(kind)
+
+
+# --------------------------------------------------------------------------
+# Tie-dense map fixtures (map2.json): palettes whose midpoints are exact
+# distance ties, palettes at the map's candidate-count thresholds (3 compact
+# inline, 7 inline, 32 per-cell cap) and palettes above 1024 entries (the
+# second map kernel, u16 region lists), mapped on probe pixels built from the
+# palette itself.
+def map2_palette_specs():
+    specs = [{"k": 512, "kind": "lattice", "step": 32, "seed": 0},
+             {"k": 4096, "kind": "lattice", "step": 16, "seed": 0},
+             {"k": 1000, "kind": "cube", "side": 10, "seed": 0},
+             {"k": 4096, "kind": "cube", "side": 16, "seed": 0}]
+    for k in (3, 4, 7, 8, 9, 32, 33, 40):
+        specs.append({"k": k, "kind": "cluster", "seed": 300 + k})
+    for k in (1025, 4096, 16384):
+        specs.append({"k": k, "kind": "random", "seed": 77 + k})
+    specs.append({"k": 16384, "kind": "sametsum", "seed": 91 + 16384})
+    specs.append({"k": 2048, "kind": "dups", "seed": 5 + 2048})
+    specs.append({"k": 125, "kind": "subdivided", "seed": 0})
+    specs.append({"k": 2, "kind": "gray", "seed": 3})
+    return specs
+
+
+def map2_cube_specs():
+    """Palettes mapped over all 2^24 colours (np.arange(1 << 24))."""
+    return [{"k": 125, "kind": "subdivided", "seed": 0}, {"k": 16, "kind": "random", "seed": 77 + 16}]
+
+
+def map2_seed(spec):
+    return 40000 + 131 * spec["k"] + 7 * spec["seed"] + len(spec["kind"])
+
+
+def _channels(p):
+    return (p >> 16) & 0xFF, (p >> 8) & 0xFF, p & 0xFF
+
+
+def _midpoints(a, b):
+    """Per-channel floor midpoint of colour pairs."""
+    ca, cb = _channels(a.astype(np.uint32)), _channels(b.astype(np.uint32))
+    m = [(x + y) >> 1 for x, y in zip(ca, cb)]
+    return ((m[0] << 16) | (m[1] << 8) | m[2]).astype(np.uint32)
+
+
+MAP_PROBE_PAIRS = 12000   # random-pair midpoints: the first of part (ii)
+
+
+def map_probe_parts(pal, seed):
+    """The parts of map_probe_pixels, top byte clear: (i) every palette entry,
+    (ii) midpoints of MAP_PROBE_PAIRS random entry pairs, then of the pairs
+    adjacent in R+G+B order (at most 8000), (iii) the 8 corners of 1000 cells,
+    (iv) uniform pixels."""
+    pal = np.ascontiguousarray(pal, np.uint32) & np.uint32(0xFFFFFF)
+    k = len(pal)
+    r = xorshift(2 * MAP_PROBE_PAIRS + 3000, seed=SEED ^ (seed * 0x100000001B3))
+    a, b = pal[r[:MAP_PROBE_PAIRS] % k], pal[r[MAP_PROBE_PAIRS:2 * MAP_PROBE_PAIRS] % k]
+    ch = _channels(pal)
+    by_sum = pal[np.argsort((ch[0] + ch[1] + ch[2]).astype(np.int64), kind="stable")]
+    adj = _midpoints(by_sum[:-1], by_sum[1:])[:8000]
+    c = (r[2 * MAP_PROBE_PAIRS:] % 32).reshape(1000, 3) * 8
+    corners = []
+    for m in range(8):
+        x = [c[:, i] + (7 if (m >> i) & 1 else 0) for i in range(3)]
+        corners.append((x[0] << 16) | (x[1] << 8) | x[2])
+    corners = np.stack(corners, 1).reshape(-1).astype(np.uint32)
+    return {"entries": pal.copy(), "mid": np.concatenate([_midpoints(a, b), adj]), "corners": corners,
+            "uniform": xorshift(20000, seed=seed + 1)}
+
+
+def map_probe_pixels(pal, seed):
+    """Probe pixels of a palette: map_probe_parts concatenated, more uniform
+    pixels up to a length = 5 (mod 8) (ragged for the 8-pixel groups), and
+    (v) a garbage top byte in every pixel (the map ignores bits 24-31)."""
+    parts = map_probe_parts(pal, seed)
+    px = np.concatenate([parts["entries"], parts["mid"], parts["corners"], parts["uniform"]])
+    pad = (5 - len(px)) % 8
+    px = np.concatenate([px, xorshift(pad + 1, seed=seed + 2)[:pad]])
+    assert len(px) % 8 == 5
+    return (px | ((xorshift(len(px), seed=seed + 3) & 0xFF) << 24)).astype(np.uint32)
 
 
 # --------------------------------------------------------------------------

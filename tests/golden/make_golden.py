@@ -23,7 +23,8 @@ are regenerated from the reference itself by this script and are the pin.
 
 Fixture files (all data, no code): kats.json, cases.json/.npz, c1.npz,
 big.json/.npz, png.json/.npz, map.json, weighted.json, varpart.json/.npz, png/*.png (the two
-sample images the reference ships in tests/).
+sample images the reference ships in tests/), and map2.json (--only map2: it needs only
+libdqref.so and rewrites no other fixture).
 """
 import argparse
 import ctypes
@@ -149,7 +150,9 @@ def main():
     ap.add_argument("--jobs", type=int, default=3, help="worker processes for the c4 section")
     a = ap.parse_args()
     only = set(a.only.split(",")) if a.only else None
-    ref, instr = Ref(REF_SO), Ref(INSTR_SO)
+    ref = Ref(REF_SO)
+    # (the map sections need only the plain build: --only map2 runs without instrument_ref.sh)
+    instr = Ref(INSTR_SO) if only is None or not only <= {"map", "map2", "utils"} else None
 
     def want(s):
         return only is None or s in only
@@ -234,6 +237,26 @@ def main():
             res.append({"spec": spec, "out_fnv": "%016x" % fx.fnv(out),
                         "first": [int(v) for v in out[:64]]})
         fx.dump_json("map.json", res)
+
+    # ---- 6b. map_colors_mps on tie-dense probe pixels (entries, pair midpoints,
+    #        cell corners, garbage top bytes) of lattice / dense / threshold /
+    #        large palettes, and over all 2^24 colours for two small palettes
+    #        (explicit only: the other fixtures are not regenerated with it)
+    if only is not None and "map2" in only:
+        res = {"palettes": [], "cubes": []}
+        for spec in fx.map2_palette_specs():
+            pal = fx.make_palette(spec)
+            px = fx.map_probe_pixels(pal, fx.map2_seed(spec))
+            out = ref.map_colors(px, pal)
+            res["palettes"].append({"spec": spec, "n_px": int(len(px)), "out_fnv": "%016x" % fx.fnv(out),
+                                    "first": [int(v) for v in out[:64]]})
+            print("map2", spec, len(px), flush=True)
+        cube = np.arange(1 << 24, dtype=np.uint32)
+        for spec in fx.map2_cube_specs():
+            out = ref.map_colors(cube, fx.make_palette(spec))
+            res["cubes"].append({"spec": spec, "out_fnv": "%016x" % fx.fnv(out)})
+            print("map2 cube", spec, flush=True)
+        fx.dump_json("map2.json", res)
 
     # ---- 7. weighted path (allPixelsUnique=0) on synthetic inputs
     if want("weighted"):

@@ -162,6 +162,76 @@ def test_map_equals_argmin_distance_rank():
         assert np.array_equal(got, want), trial
 
 
+def oracle_map_argmin(px, pal):
+    px = np.ascontiguousarray(px, np.uint32)
+    pal = np.ascontiguousarray(pal, np.uint32)
+    got = np.zeros(len(px), np.uint32)
+    fx.oracle().dqo_map_argmin(fx.vp(px), ctypes.c_uint32(len(px)), fx.vp(got), fx.vp(pal), ctypes.c_int(len(pal)))
+    return got
+
+
+MAP2 = fx.load_json("map2.json")
+
+
+def test_map2_covers_the_specs():
+    assert [c["spec"] for c in MAP2["palettes"]] == fx.map2_palette_specs()
+    assert [c["spec"] for c in MAP2["cubes"]] == fx.map2_cube_specs()
+
+
+@pytest.mark.parametrize("i", range(len(MAP2["palettes"])),
+                         ids=["%s%d" % (c["spec"]["kind"], c["spec"]["k"]) for c in MAP2["palettes"]])
+def test_map2_palettes(i):
+    """The oracle's walk on the tie-dense probe pixels (entries, pair midpoints,
+    cell corners, garbage top bytes) against the reference's outputs, and the
+    identity the GPU kernels rely on -- the walk == argmin over (squared
+    distance, visit rank) -- up to 16384 entries (on those, 10000 pixels)."""
+    c = MAP2["palettes"][i]
+    pal = fx.make_palette(c["spec"])
+    px = fx.map_probe_pixels(pal, fx.map2_seed(c["spec"]))
+    assert len(px) == c["n_px"] and len(px) % 8 == 5
+    out = oracle_map(px, pal)
+    assert "%016x" % fx.fnv(out) == c["out_fnv"], c["spec"]
+    assert [int(v) for v in out[:64]] == c["first"]
+    m = 10000 if len(pal) >= 16384 else len(px)
+    assert np.array_equal(oracle_map_argmin(px[:m], pal), out[:m]), c["spec"]
+
+
+@pytest.mark.parametrize("i", range(len(MAP2["cubes"])), ids=["subdivided125", "random16"])
+def test_map2_full_cube(i):
+    """Every one of the 2^24 colours."""
+    c = MAP2["cubes"][i]
+    out = oracle_map(np.arange(1 << 24, dtype=np.uint32), fx.make_palette(c["spec"]))
+    assert "%016x" % fx.fnv(out) == c["out_fnv"], c["spec"]
+
+
+def _tie_multiplicity(px, pal):
+    """Per pixel: how many DIFFERENT palette colours are at the minimum squared distance."""
+    pal = np.unique(np.asarray(pal, np.uint32) & np.uint32(0xFFFFFF))
+    p = np.stack([(px >> 16) & 0xFF, (px >> 8) & 0xFF, px & 0xFF], 1).astype(np.int64)
+    q = np.stack([(pal >> 16) & 0xFF, (pal >> 8) & 0xFF, pal & 0xFF], 1).astype(np.int64)
+    mult = np.zeros(len(px), np.int64)
+    for s in range(0, len(px), 500):
+        d = ((p[s:s + 500, None, :] - q[None, :, :]) ** 2).sum(2)
+        mult[s:s + 500] = (d == d.min(1, keepdims=True)).sum(1)
+    return mult
+
+
+@pytest.mark.parametrize("spec", [fx.map2_palette_specs()[0], fx.map2_palette_specs()[1], fx.map2_cube_specs()[0]],
+                         ids=["lattice512", "lattice4096", "subdivided125"])
+def test_map2_probe_pixels_are_tie_dense(spec):
+    """What keeps the inputs honest: of the first 4000 midpoint pixels at least
+    half are at exactly the same distance from two or more different palette
+    colours, and some from four or more -- only the rank field of the map's
+    key and the strictness of its dominance filter decide those."""
+    assert spec["kind"] in ("lattice", "subdivided")
+    pal = fx.make_palette(spec)
+    mid = fx.map_probe_parts(pal, fx.map2_seed(spec))["mid"][:4000]
+    assert len(mid) == 4000
+    mult = _tie_multiplicity(mid, pal)
+    assert (mult >= 2).sum() >= 2000, (mult >= 2).sum()
+    assert mult.max() >= 4, mult.max()
+
+
 def oracle_quant_weighted(px, k):
     orc = fx.oracle()
     px = np.ascontiguousarray(px, np.uint32)
