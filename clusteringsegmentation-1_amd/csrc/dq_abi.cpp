@@ -17,7 +17,6 @@
 #include <mutex>
 #include <thread>
 #include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "../../include/DivQuantHeader.h"
@@ -48,16 +47,6 @@ int current_device() {
 bool quiet() {
   const char* q = std::getenv("DQ_HIP_QUIET");
   return q && *q && *q != '0';
-}
-
-// First-occurrence colortable dedup (quant_util.cpp:93-118).
-uint32_t dedup_colortable(uint32_t* ct, uint32_t k) {
-  std::unordered_set<uint32_t> seen;
-  seen.reserve(k * 2 + 1);
-  uint32_t m = 0;
-  for (uint32_t i = 0; i < k; ++i)
-    if (seen.insert(ct[i]).second) ct[m++] = ct[i];
-  return m;
 }
 
 void report_empty(int num_empty) {
@@ -994,7 +983,8 @@ void quant_recurse(uint32_t numPixels, const uint32_t* inPixelsPtr, uint32_t* ou
     const long el = timediff(t1, t2);
     std::printf("quant_varpart_fast() elapsed: %ld ms aka %0.2f s\n", el, el / 1000.0f);
   }
-  k = dedup_colortable(outColortablePtr, k);
+  std::vector<uint32_t> scratch;
+  k = (uint32_t)dq::dedup_colortable(outColortablePtr, (int)k, scratch);
   *numClustersPtr = k;
   e.map(e.staged_in(), numPixels, e.staged_out(), outColortablePtr, (int)k, st);
   DQ_HIP(hipMemcpyAsync(outPixelsPtr, e.staged_out(), (size_t)numPixels * 4,

@@ -1,5 +1,6 @@
 // dq_engine.cpp -- host side of the DivQuant hot path (see dq_engine.h).
 #include "dq_engine.h"
+#include "dq_rules.h"
 #include "dq_weighted.h"
 
 #include <rccl/rccl.h>
@@ -16,7 +17,6 @@
 #include <deque>
 #include <functional>
 #include <string>
-#include <unordered_set>
 
 namespace dq {
 
@@ -52,15 +52,62 @@ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // a multiple of 4 words (the next copy starts 16-B aligned)
 inline size_t bgr_words(size_t n) { return ((3 * align16(n) + 64) / 4 + 3) & ~(size_t)3; }
 
-// Split-pass threshold (:473): cut_pos < v <=> v >= thr for integer v.
-int32_t split_threshold(double cut) {
-  if (!(cut == cut)) return 256;
-  if (cut < 0.0) return 0;
-  if (cut >= 255.0) return 256;
-  return (int32_t)std::floor(cut) + 1;
+// The cut a node's split runs with (:388-403, from its own mean / variance),
+// kept for the split pass and the children's boxes.
+void set_cut(Node& n) {
+  const Cut c = choose_cut(n.mean, n.var);
+  n.axis = (int16_t)c.axis;
+  n.thr = (int16_t)split_threshold(c.pos);
+}
+
+// The two children of node `id` (p) from its split's results: old half, new
+// half.  Their boxes are the parent's, clipped at its cut (set_cut) when the
+// halves are proven to be the cut's: v_axis < thr | >= thr.
+void make_children(const Node& p, int id, const NodeResult& r, Node* co, Node* cn) {
+  co->frame = cn->frame = p.frame;
+  co->parent = cn->parent = id;
+  co->w = r.ow;
+  cn->w = r.nw;
+  for (int c = 0; c < 3; ++c) {
+    co->mean[c] = r.om[c];
+    cn->mean[c] = r.nm[c];
+    co->var[c] = r.ov[c];
+    cn->var[c] = r.nv[c];
+    co->lo[c] = cn->lo[c] = p.lo[c];
+    co->hi[c] = cn->hi[c] = p.hi[c];
+  }
+  if (r.proven) {
+    co->hi[p.axis] = (int16_t)clip_old_hi(p.hi[p.axis], p.thr);
+    cn->lo[p.axis] = (int16_t)clip_new_lo(p.lo[p.axis], p.thr);
+  }
+  co->tse = r.tse_old;
+  cn->tse = r.tse_new;
+  cn->glen = r.n_new;
+  co->glen = p.glen - r.n_new;
+  co->buf = cn->buf = child_buf(p.buf);
 }
 
 }  // namespace
+
+// First-occurrence colortable dedup (quant_util.cpp:93-118) with a flat
+// open-addressing set (a node-allocating unordered_set cost ~100 us per
+// 8-frame call); slot value = colour + 1, 0 = empty.  `table` is scratch.
+int dedup_colortable(uint32_t* ct, int k, std::vector<uint32_t>& table) {
+  size_t cap = 16;
+  while (cap < 2 * (size_t)k) cap <<= 1;
+  table.assign(cap, 0u);
+  int m = 0;
+  for (int i = 0; i < k; ++i) {
+    const uint32_t c = ct[i];
+    size_t h = (size_t)((c * 2654435761u) >> 7) & (cap - 1);
+    while (table[h] != 0 && table[h] != c + 1) h = (h + 1) & (cap - 1);
+    if (table[h] == 0) {
+      table[h] = c + 1;
+      ct[m++] = c;
+    }
+  }
+  return m;
+}
 
 double Engine::host_us_now() { return host_us(); }
 
@@ -432,17 +479,12 @@ const uint8_t* Engine::buf_ptr(int buf, const FrameState& f, int shard) const {
 // Tile length of a round of `total` points: whole 4096-point sweeps, about
 // tiles_target_ tiles, at most tile_max_ points.  A record gets at least
 // node_tiles_ tiles (a node still active late in a round is then swept by
-// several workgroups, not one).  plan_kernel restates both (plan_tile_len).
+// several workgroups, not one): the record's own tiling is dq_rules.h's
+// tile_len_of / ntiles_of, for the host and for plan_kernel.
 uint64_t Engine::round_tile_len(uint64_t total) const {
   uint64_t tl = (total + tiles_target_ - 1) / tiles_target_;
   tl = ((tl + kSweep - 1) / kSweep) * kSweep;
   return std::max<uint64_t>(kSweep, std::min<uint64_t>(tl, tile_max_));
-}
-
-uint64_t Engine::tile_len_of(uint64_t len, uint64_t tl) const {
-  uint64_t t = (len + node_tiles_ - 1) / node_tiles_;
-  t = ((t + kSweep - 1) / kSweep) * kSweep;
-  return std::max<uint64_t>(kSweep, std::min<uint64_t>(tl, t));
 }
 
 // The source format of every node in `ids` (a partition launch's parents):
@@ -457,6 +499,52 @@ int Engine::src_fmt(const std::vector<int>& ids) const {
     f = g;
   }
   return f < 0 ? FMT_ANY : f;
+}
+
+// The layout of a round's arena block (RoundBlock, dq_engine.h) for nr
+// records, room for `tiles` tiles and `ptiles` part tiles, and `extra` bytes
+// of the caller's between the part tiles and the counters.
+Engine::RoundBlock Engine::round_block(size_t nr, size_t tiles, size_t ptiles, size_t extra, int max_iters) {
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  RoundBlock b;
+  b.o_tiles = al(nr * sizeof(DevNode));
+  b.o_pt = b.o_tiles + al(tiles * sizeof(Tile));
+  b.o_extra = b.o_pt + al(ptiles * sizeof(PartTile));
+  b.o_ctr = b.o_extra + al(extra);
+  b.o_wp = b.o_ctr + al((size_t)(max_iters + 1) * sizeof(LaunchCtr));
+  b.o_rd = b.o_wp + al(tiles * kTileWaves * sizeof(uint32_t));
+  b.o_sum = b.o_rd + al((size_t)max_iters * nr * sizeof(uint32_t));
+  b.o_sd = b.o_sum + al(nr * sizeof(RecSummary));
+  b.bytes = b.o_sd + al(nr * sizeof(uint32_t));
+  return b;
+}
+
+// What every kernel of round R gets, whoever builds its tables: the engine's
+// buffers, the round's result / status slot, and the pointers into its block
+// at dblk.  The caller sets it, counts, ps_mode and sdone.
+void Engine::round_args(Round& R, char* dblk, const RoundBlock& b, int mode) {
+  RoundArgs& ra = R.ra;
+  ra.tiles = R.dt;
+  ra.nodes = R.dn;
+  ra.parts = d_parts_;
+  ra.parts2 = d_parts2_;
+  ra.wparts = reinterpret_cast<uint32_t*>(dblk + b.o_wp);
+  ra.ptiles = reinterpret_cast<const PartTile*>(dblk + b.o_pt);
+  ra.sparts = d_sparts_;
+  ra.hres = d_res_ + (size_t)R.par * cap_res_;
+  ra.ctr = reinterpret_cast<LaunchCtr*>(dblk + b.o_ctr);
+  ra.hstat = d_stat_ + (size_t)R.par * cap_stat_;
+  ra.seq = R.seq;
+  ra.fixed_point = fixed_point_ ? 1 : 0;
+  ra.nn = R.nr;
+  ra.tot = d_tot_;
+  ra.nshard = nshard_;
+  ra.debug = debug_;
+  ra.rdone = reinterpret_cast<uint32_t*>(dblk + b.o_rd);
+  ra.rsum = reinterpret_cast<RecSummary*>(dblk + b.o_sum);
+  ra.dres = d_dres_ + (size_t)R.par * cap_res_;
+  ra.plane = cap_px_;
+  ra.tot_mode = mode;
 }
 
 // ---------------------------------------------------------------------------
@@ -544,11 +632,7 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
   const uint64_t tl = round_tile_len(total);
   size_t ntiles = 0, nt_own = 0;
   for (int a = 0; a < nl; ++a) {   // empty records get one empty tile (their epilogue still runs)
-    for (int sh = 0; sh < S; ++sh) {
-      const uint64_t len = seg(order[a], sh).len;
-      const uint64_t tln = tile_len_of(len, tl);
-      ntiles += std::max<size_t>(1, (len + tln - 1) / tln);
-    }
+    for (int sh = 0; sh < S; ++sh) ntiles += ntiles_of(seg(order[a], sh).len, (uint32_t)tl, (uint32_t)node_tiles_);
     if (a == n_own - 1) nt_own = ntiles;
   }
   size_t nptiles = 0;
@@ -563,23 +647,10 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
   R.nptiles = R.ptiles_cap = nptiles;
   R.nt_own = nt_own;
 
-  // the round's block: [DevNode nr | Tile ntiles | PartTile nptiles | LaunchCtr max_iters+1 | wparts | rdone]
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  const size_t o_tiles = al(nr * sizeof(DevNode));
-  const size_t o_pt = o_tiles + al(ntiles * sizeof(Tile));
-  const size_t o_mpt = o_pt + al(nptiles * sizeof(PartTile));
-  const size_t o_ctr = o_mpt + al(nmat * sizeof(PartTile));
-  // (LaunchCtr and status word max_iters: the split epilogue's); then the
-  // per-(tile, wave) counts, zero from the staging memset (partsplit adds
-  // the fused children's up)
-  const size_t o_wp = o_ctr + al((size_t)(max_iters + 1) * sizeof(LaunchCtr));
-  // then the fused 2-means passes' arrival words, per (iteration, record)
-  const size_t o_rd = o_wp + al(ntiles * kTileWaves * sizeof(uint32_t));
-  // then the records' summaries (written as each becomes final; the next plan's scan)
-  const size_t o_sum = o_rd + al((size_t)max_iters * nr * sizeof(uint32_t));
-  // then the partition's per-parent arrival words (split totals folded in)
-  const size_t o_sd = o_sum + al((size_t)nr * sizeof(RecSummary));
-  const size_t bytes = o_sd + al((size_t)nr * sizeof(uint32_t));
+  // the round's block; its extra part: the PS_WRITE partition's part tiles
+  // (everything from o_ctr on is zero from the staging memset)
+  const RoundBlock blk = round_block((size_t)nr, ntiles, nptiles, nmat * sizeof(PartTile), max_iters);
+  const size_t bytes = blk.bytes;
   R.bytes = bytes;
   if (mode == TOT_ALLREDUCE) ensure_totals(nl, stream);
   // the staging is rewritten: its previous upload must have run
@@ -597,12 +668,10 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
   char* dblk = arena_alloc(bytes, stream);
   std::memset(h_stage_, 0, bytes);
   DevNode* hn = reinterpret_cast<DevNode*>(h_stage_);
-  Tile* ht = reinterpret_cast<Tile*>(h_stage_ + o_tiles);
-  PartTile* hp = reinterpret_cast<PartTile*>(h_stage_ + o_pt);
-  DevNode* dn = reinterpret_cast<DevNode*>(dblk);
-  Tile* dt = reinterpret_cast<Tile*>(dblk + o_tiles);
-  R.dn = dn;
-  R.dt = dt;
+  Tile* ht = reinterpret_cast<Tile*>(h_stage_ + blk.o_tiles);
+  PartTile* hp = reinterpret_cast<PartTile*>(h_stage_ + blk.o_pt);
+  R.dn = reinterpret_cast<DevNode*>(dblk);
+  R.dt = reinterpret_cast<Tile*>(dblk + blk.o_tiles);
   R.tbeg.assign(nr, 0);
   R.tend.assign(nr, 0);
 
@@ -624,18 +693,11 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
     frames_[n.frame].splits_queued++;
     const FrameState& fs = frames_[n.frame];
     int32_t thr = 0, shift = 0;
-    if (!root_round) {
-      // Cut axis/position (:388-403): comparisons and copies only.  (The
-      // root's come from its PASS_INIT epilogue on the device.)
-      double maxv = n.var[0], cut = n.mean[0];
-      int axis = 0;
-      if (maxv < n.var[1]) { maxv = n.var[1]; axis = 1; cut = n.mean[1]; }
-      if (maxv < n.var[2]) { axis = 2; cut = n.mean[2]; }
-      thr = split_threshold(cut);
-      shift = 16 - 8 * axis;
+    if (!root_round) {   // (the root's cut comes from its PASS_INIT epilogue: finish_round)
+      set_cut(n);
+      thr = n.thr;
+      shift = 16 - 8 * n.axis;
     }
-    n.axis = (int16_t)((16 - shift) >> 3);
-    n.thr = (int16_t)thr;
     for (int sh = 0; sh < S; ++sh) {
       DevNode& d = hn[a * S + sh];
       d.src = buf_ptr(n.buf, fs, sh);
@@ -659,7 +721,7 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
       d.prm.shift = shift;
       for (int c = 0; c < 3; ++c) { d.box_lo[c] = n.lo[c]; d.box_hi[c] = n.hi[c]; }
       d.tile_begin = t;
-      const uint64_t tln = tile_len_of(sg.len, tl);
+      const uint64_t tln = tile_len_of(sg.len, (uint32_t)tl, (uint32_t)node_tiles_);
       d.tile_len = (uint32_t)tln;
       for (uint64_t o = 0; o == 0 || o < sg.len; o += tln) {
         Tile& tt = ht[t++];
@@ -703,7 +765,7 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
     }
   }
   {   // the PS_WRITE partition's part tiles (no children split: nothing summed or counted)
-    PartTile* hm = reinterpret_cast<PartTile*>(h_stage_ + o_mpt);
+    PartTile* hm = reinterpret_cast<PartTile*>(h_stage_ + blk.o_extra);
     int q = 0;
     for (int p : mat)
       for (int sh = 0; sh < S; ++sh) {
@@ -729,39 +791,19 @@ int Engine::enqueue_host_round(const std::vector<int>& active_in, bool root_roun
   R.seq = ++seq_;
   R.par = (int)(R.seq % kSlots);
   RoundArgs& ra = R.ra;
-  ra.tiles = dt;
-  ra.nodes = dn;
-  ra.parts = d_parts_;
-  ra.parts2 = d_parts2_;
-  ra.wparts = reinterpret_cast<uint32_t*>(dblk + o_wp);
-  ra.ptiles = reinterpret_cast<const PartTile*>(dblk + o_pt);
-  ra.sparts = d_sparts_;
-  ra.hres = d_res_ + (size_t)R.par * cap_res_;
-  ra.ctr = reinterpret_cast<LaunchCtr*>(dblk + o_ctr);
-  ra.hstat = d_stat_ + (size_t)R.par * cap_stat_;
-  ra.seq = R.seq;
-  ra.fixed_point = fixed_point_ ? 1 : 0;
+  round_args(R, dblk, blk, mode);
   ra.it = 0;
-  ra.nn = nr;
-  ra.tot = d_tot_;
-  ra.nshard = S;
-  ra.debug = debug_;
-  ra.rdone = reinterpret_cast<uint32_t*>(dblk + o_rd);
-  ra.rsum = reinterpret_cast<RecSummary*>(dblk + o_sum);
-  ra.dres = d_dres_ + (size_t)R.par * cap_res_;
   ra.counts = nullptr;
-  ra.plane = cap_px_;
-  ra.tot_mode = mode;
   ra.ps_mode = PS_FULL;
   // allreduced totals with one shard and every record a partitioned parent's
   // child: the partition's last workgroups write the split totals (no
   // nodesum_kernel launch)
   const bool fold = fold_split_ && mode == TOT_ALLREDUCE && S == 1 && n_own == 0 && nptiles > 0;
-  ra.sdone = fold ? reinterpret_cast<uint32_t*>(dblk + o_sd) : nullptr;
+  ra.sdone = fold ? reinterpret_cast<uint32_t*>(dblk + blk.o_sd) : nullptr;
   if (nmat > 0) {
     RoundArgs ma = ra;
     ma.sdone = nullptr;
-    ma.ptiles = reinterpret_cast<const PartTile*>(dblk + o_mpt);
+    ma.ptiles = reinterpret_cast<const PartTile*>(dblk + blk.o_extra);
     ma.ps_mode = PS_WRITE;
     timed_begin(stream);
     launch_partsplit(ma, (int)nmat, src_fmt(mat), stream);
@@ -897,22 +939,13 @@ int Engine::enqueue_planned_round(int prev, const std::vector<int32_t>& plist, i
                                  total / R.tl + (size_t)R.nr * (node_tiles_ + 1) + 1);
   R.ptiles_cap = P.tiles_cap;
   DQ_CHECK(R.tiles_cap <= cap_parts_ && 2 * R.ptiles_cap <= cap_sparts_, "planned round above the tile capacity");
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  const size_t nr = (size_t)R.nr;
-  const size_t o_tiles = al(nr * sizeof(DevNode));
-  const size_t o_pt = o_tiles + al(R.tiles_cap * sizeof(Tile));
-  const size_t o_cnt = o_pt + al(R.ptiles_cap * sizeof(PartTile));
-  const size_t o_ctr = o_cnt + 64;
-  const size_t o_wp = o_ctr + al((size_t)(max_iters + 1) * sizeof(LaunchCtr));
-  const size_t o_rd = o_wp + al(R.tiles_cap * kTileWaves * sizeof(uint32_t));
-  const size_t o_sum = o_rd + al((size_t)max_iters * nr * sizeof(uint32_t));
-  const size_t o_sd = o_sum + al(nr * sizeof(RecSummary));   // (the partition's per-parent arrivals)
-  const size_t bytes = o_sd + al(nr * sizeof(uint32_t));     // ([o_ctr, bytes): zero on entry)
-  R.bytes = bytes;
-  char* dblk = arena_alloc(bytes, stream);
+  // the round's block; its extra part: the plan's counts
+  const RoundBlock blk = round_block((size_t)R.nr, R.tiles_cap, R.ptiles_cap, 64, max_iters);
+  R.bytes = blk.bytes;
+  char* dblk = arena_alloc(blk.bytes, stream);
   R.dn = reinterpret_cast<DevNode*>(dblk);
-  R.dt = reinterpret_cast<Tile*>(dblk + o_tiles);
-  R.dcounts = reinterpret_cast<uint32_t*>(dblk + o_cnt);
+  R.dt = reinterpret_cast<Tile*>(dblk + blk.o_tiles);
+  R.dcounts = reinterpret_cast<uint32_t*>(dblk + blk.o_extra);
   R.seq = ++seq_;
   R.par = (int)(R.seq % kSlots);
   // the plan list: identity unless some frames do not speculate
@@ -934,7 +967,7 @@ int Engine::enqueue_planned_round(int prev, const std::vector<int32_t>& plist, i
   pa.ptiles_cap = (uint32_t)R.ptiles_cap;
   pa.cn = R.dn;
   pa.ct = R.dt;
-  pa.cpt = reinterpret_cast<PartTile*>(dblk + o_pt);
+  pa.cpt = reinterpret_cast<PartTile*>(dblk + blk.o_pt);
   pa.counts = R.dcounts;
   pa.hcounts = d_counts_h_ + 4 * R.par;
   pa.p0 = reinterpret_cast<const uint8_t*>(d_p0_);
@@ -944,34 +977,14 @@ int Engine::enqueue_planned_round(int prev, const std::vector<int32_t>& plist, i
   pa.nshard = S;
   pa.cancel = cancel;
   RoundArgs& ra = R.ra;
-  ra.tiles = R.dt;
-  ra.nodes = R.dn;
-  ra.parts = d_parts_;
-  ra.parts2 = d_parts2_;
-  ra.wparts = reinterpret_cast<uint32_t*>(dblk + o_wp);
-  ra.ptiles = pa.cpt;
-  ra.sparts = d_sparts_;
-  ra.hres = d_res_ + (size_t)R.par * cap_res_;
-  ra.ctr = reinterpret_cast<LaunchCtr*>(dblk + o_ctr);
-  ra.hstat = d_stat_ + (size_t)R.par * cap_stat_;
-  ra.seq = R.seq;
-  ra.fixed_point = fixed_point_ ? 1 : 0;
+  if (mode == TOT_ALLREDUCE) ensure_totals(R.nl, stream);   // (before round_args: it may move d_tot_)
+  round_args(R, dblk, blk, mode);
   ra.it = max_iters;
-  ra.nn = R.nr;
-  if (mode == TOT_ALLREDUCE) ensure_totals(R.nl, stream);
-  ra.tot = d_tot_;
-  ra.nshard = S;
-  ra.debug = debug_;
-  ra.rdone = reinterpret_cast<uint32_t*>(dblk + o_rd);
-  ra.rsum = reinterpret_cast<RecSummary*>(dblk + o_sum);
-  ra.dres = d_dres_ + (size_t)R.par * cap_res_;
   ra.counts = R.dcounts;
-  ra.plane = cap_px_;
-  ra.tot_mode = mode;
   ra.ps_mode = R.stats_only ? PS_STATS : PS_FULL;
   // (split totals folded into the partition, as in enqueue_host_round)
   const bool fold = fold_split_ && mode == TOT_ALLREDUCE && S == 1;
-  ra.sdone = fold ? reinterpret_cast<uint32_t*>(dblk + o_sd) : nullptr;
+  ra.sdone = fold ? reinterpret_cast<uint32_t*>(dblk + blk.o_sd) : nullptr;
   // the plan and the partition in one launch (arena block zero) for rounds of
   // about one wave of partition workgroups (4 per CU) over at most one 4K
   // frame's points: there the plan's launch and round trips are on the
@@ -1039,19 +1052,11 @@ void Engine::assign_planned(int ri) {
     Node& n = nodes_[R.order[a]];
     n.queued = true;
     for (int sh = 0; sh < S; ++sh) {   // records a * S + sh, tiles in record order
-      const uint64_t len = seg(R.order[a], sh).len;
-      const uint64_t tln = tile_len_of(len, R.tl);
       R.tbeg[a * S + sh] = t;
-      t += (int32_t)std::max<uint64_t>(1, (len + tln - 1) / tln);
+      t += (int32_t)ntiles_of(seg(R.order[a], sh).len, (uint32_t)R.tl, (uint32_t)node_tiles_);
       R.tend[a * S + sh] = t;
     }
-    // the cut the plan chose (:388-403), for the children's boxes
-    double maxv = n.var[0], cut = n.mean[0];
-    int axis = 0;
-    if (maxv < n.var[1]) { maxv = n.var[1]; axis = 1; cut = n.mean[1]; }
-    if (maxv < n.var[2]) { axis = 2; cut = n.mean[2]; }
-    n.axis = (int16_t)axis;
-    n.thr = (int16_t)split_threshold(cut);
+    set_cut(n);   // the cut the plan chose, for the children's boxes
   }
   for (int p : R.parents)
     for (int sh = 0; sh < S; ++sh) npt += seg(p, sh).ntiles;
@@ -1296,42 +1301,11 @@ int Engine::finish_round(int ri, int max_iters, hipStream_t stream, bool specula
     const NodeResult& r = res[a * S];   // global results: every record agrees
     if (R.root) {
       for (int c = 0; c < 3; ++c) { nodes_[id].mean[c] = r.tm[c]; nodes_[id].var[c] = r.tv[c]; }
-      // the cut the INIT epilogue chose on the device, same comparisons
-      double maxv = r.tv[0], cut = r.tm[0];
-      int axis = 0;
-      if (maxv < r.tv[1]) { maxv = r.tv[1]; axis = 1; cut = r.tm[1]; }
-      if (maxv < r.tv[2]) { axis = 2; cut = r.tm[2]; }
-      nodes_[id].axis = (int16_t)axis;
-      nodes_[id].thr = (int16_t)split_threshold(cut);
+      set_cut(nodes_[id]);   // the cut the INIT epilogue chose on the device
     }
     Node co, cn;
     const int io = (int)nodes_.size();
-    {
-      const Node& p = nodes_[id];
-      co.frame = cn.frame = p.frame;
-      co.parent = cn.parent = id;
-      co.w = r.ow;
-      cn.w = r.nw;
-      for (int c = 0; c < 3; ++c) {
-        co.mean[c] = r.om[c];
-        cn.mean[c] = r.nm[c];
-        co.var[c] = r.ov[c];
-        cn.var[c] = r.nv[c];
-      }
-      co.tse = r.tse_old;
-      cn.tse = r.tse_new;
-      cn.glen = r.n_new;
-      co.glen = p.glen - r.n_new;
-      co.buf = cn.buf = child_buf(p.buf);
-      for (int c = 0; c < 3; ++c) {
-        co.lo[c] = cn.lo[c] = p.lo[c];
-        co.hi[c] = cn.hi[c] = p.hi[c];
-      }
-      if (r.proven) {   // the halves are the cut's: v_axis < thr | >= thr
-        co.hi[p.axis] = (int16_t)std::min<int>(p.hi[p.axis], p.thr - 1);
-        cn.lo[p.axis] = (int16_t)std::max<int>(p.lo[p.axis], p.thr);
-      }
-    }
+    make_children(nodes_[id], id, r, &co, &cn);
     nodes_.push_back(co);
     nodes_.push_back(cn);
     segs_.resize((size_t)(io + 2) * S);
@@ -1674,22 +1648,7 @@ void Engine::run(FrameJob* jobs, int nframes, int max_iters, bool dedup_map,
     std::vector<uint32_t> table;
     for (auto& f : frames_) {
       FrameJob& j = *f.job;
-      // First-occurrence colortable dedup (quant_util.cpp:93-118) with a flat
-      // open-addressing set (a node-allocating unordered_set cost ~100 us per
-      // 8-frame call); slot value = colour + 1, 0 = empty.
-      size_t cap = 16;
-      while (cap < 2 * (size_t)j.k_out) cap <<= 1;
-      table.assign(cap, 0u);
-      int m = 0;
-      for (int i = 0; i < j.k_out; ++i) {
-        const uint32_t c = j.ct[i];
-        size_t h = (size_t)((c * 2654435761u) >> 7) & (cap - 1);
-        while (table[h] != 0 && table[h] != c + 1) h = (h + 1) & (cap - 1);
-        if (table[h] == 0) {
-          table[h] = c + 1;
-          j.ct[m++] = c;
-        }
-      }
+      const int m = dedup_colortable(j.ct, j.k_out, table);
       j.k_out = m;
       if (j.d_out)   // every shard's rows with the frame's palette
         for (int sh = 0; sh < S; ++sh)
@@ -1883,8 +1842,8 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
     }
     const int nt = (int)tiles.size();
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_tiles = al((size_t)nn * sizeof(WState));
-    const size_t up_bytes = o_tiles + al((size_t)nt * sizeof(WTile));
+    const size_t o_wtiles = al((size_t)nn * sizeof(WState));
+    const size_t up_bytes = o_wtiles + al((size_t)nt * sizeof(WTile));
     const size_t o_tsum = up_bytes;
     const size_t o_tpre = o_tsum + al((size_t)nt * 8 * sizeof(double));
     const size_t o_fold = o_tpre + al((size_t)nt * 8 * sizeof(double));
@@ -1936,16 +1895,13 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
         w.box_hi[c] = nd.hi[c];
       }
       if (!w.root) {   // the cut (:388-403); the root's comes from its init folds
-        double maxv = nd.var[0], cut = nd.mean[0];
-        int axis = 0;
-        if (maxv < nd.var[1]) { maxv = nd.var[1]; axis = 1; cut = nd.mean[1]; }
-        if (maxv < nd.var[2]) { axis = 2; cut = nd.mean[2]; }
-        w.axis = axis;
-        w.cut = cut;
+        const Cut cut = choose_cut(nd.mean, nd.var);
+        w.axis = cut.axis;
+        w.cut = cut.pos;
       }
       w.done_it = -1;
     }
-    std::memcpy(h_stage_ + o_tiles, tiles.data(), (size_t)nt * sizeof(WTile));
+    std::memcpy(h_stage_ + o_wtiles, tiles.data(), (size_t)nt * sizeof(WTile));
     char* db = static_cast<char*>(d_wnodes_);
     launch_upload(db, d_stage_view_, up_bytes, stream);
     DQ_HIP(hipEventRecord(stage_ev_, stream));
@@ -1964,7 +1920,7 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
     *h_active = 0u;
     WArgs wa;
     wa.nodes = reinterpret_cast<WState*>(db);
-    wa.tiles = reinterpret_cast<const WTile*>(db + o_tiles);
+    wa.tiles = reinterpret_cast<const WTile*>(db + o_wtiles);
     wa.norm = norm;
     wa.tsum = reinterpret_cast<double*>(db + o_tsum);
     wa.tpre = reinterpret_cast<double*>(db + o_tpre);
@@ -2002,40 +1958,11 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
       last_seq_tiles += (uint32_t)r.pad;
       if (id == 0)
         for (int c = 0; c < 3; ++c) { nodes_[0].mean[c] = r.tm[c]; nodes_[0].var[c] = r.tv[c]; }
-      {   // the cut the split ran with (the children's boxes)
-        const Node& n = nodes_[id];
-        double maxv = n.var[0], cut = n.mean[0];
-        int axis = 0;
-        if (maxv < n.var[1]) { maxv = n.var[1]; axis = 1; cut = n.mean[1]; }
-        if (maxv < n.var[2]) { axis = 2; cut = n.mean[2]; }
-        nodes_[id].axis = (int16_t)axis;
-        nodes_[id].thr = (int16_t)split_threshold(cut);
-      }
+      set_cut(nodes_[id]);   // the cut the split ran with (the children's boxes)
       DQ_CHECK(r.n_new_local == (uint32_t)r.n_new, "weighted partition count differs from the fold count");
       Node co, cn;
       const int io = (int)nodes_.size();
-      const Node& p = nodes_[id];
-      co.frame = cn.frame = 0;
-      co.parent = cn.parent = id;
-      co.w = r.ow;
-      cn.w = r.nw;
-      for (int c = 0; c < 3; ++c) {
-        co.mean[c] = r.om[c];
-        cn.mean[c] = r.nm[c];
-        co.var[c] = r.ov[c];
-        cn.var[c] = r.nv[c];
-        co.lo[c] = cn.lo[c] = p.lo[c];
-        co.hi[c] = cn.hi[c] = p.hi[c];
-      }
-      if (r.proven) {   // the halves are the cut's: v_axis < thr | >= thr
-        co.hi[p.axis] = (int16_t)std::min<int>(p.hi[p.axis], p.thr - 1);
-        cn.lo[p.axis] = (int16_t)std::max<int>(p.lo[p.axis], p.thr);
-      }
-      co.tse = r.tse_old;
-      cn.tse = r.tse_new;
-      cn.glen = r.n_new;
-      co.glen = p.glen - r.n_new;
-      co.buf = cn.buf = child_buf(p.buf);
+      make_children(nodes_[id], id, r, &co, &cn);
       nodes_.push_back(co);
       nodes_.push_back(cn);
       segs_.resize((size_t)(io + 2));
@@ -2059,19 +1986,8 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
   }
   finish_frame(f, true);
   if (dedup_map) {
-    size_t cap = 16;
-    while (cap < 2 * (size_t)job.k_out) cap <<= 1;
-    std::vector<uint32_t> table(cap, 0u);
-    int m = 0;
-    for (int i = 0; i < job.k_out; ++i) {   // first-occurrence dedup (quant_util.cpp:93-118)
-      const uint32_t c = job.ct[i];
-      size_t h = (size_t)((c * 2654435761u) >> 7) & (cap - 1);
-      while (table[h] != 0 && table[h] != c + 1) h = (h + 1) & (cap - 1);
-      if (table[h] == 0) {
-        table[h] = c + 1;
-        job.ct[m++] = c;
-      }
-    }
+    std::vector<uint32_t> table;
+    const int m = dedup_colortable(job.ct, job.k_out, table);
     job.k_out = m;
     if (job.d_out) map(job.d_in, job.n, job.d_out, job.ct, m, stream);
   }

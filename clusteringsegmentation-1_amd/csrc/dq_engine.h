@@ -105,6 +105,10 @@ struct FrameJob {
   int num_empty = 0;                 // empty clusters (:1067-1069)
 };
 
+// First-occurrence dedup of ct[0..k) in place (quant_util.cpp:93-118);
+// returns the colours kept.  `table` is scratch.
+int dedup_colortable(uint32_t* ct, int k, std::vector<uint32_t>& table);
+
 // Per-kernel-kind timing (filled only when timing is enabled).
 struct KernelStat {
   uint64_t launches = 0;
@@ -323,6 +327,24 @@ class Engine {
     long loop_event = -1;             // kloop_kernel's timing event (pending_ index)
     double t_enq = 0;
   };
+  // A round's block in the arena, 64-B aligned parts at these byte offsets:
+  //   [DevNode nr | Tile | PartTile | extra | LaunchCtr max_iters + 1 | wparts | rdone | rsum | sdone]
+  // `extra` is the builder's: a host round's PS_WRITE part tiles, a planned
+  // round's counts.  The tables before o_ctr are written by the builder
+  // (staging upload / plan_kernel).  [o_ctr, bytes) must be ZERO when the
+  // round's first kernel runs: a host round uploads it zeroed with its
+  // tables, a planned round relies on the arena being zero (Engine::run
+  // clears what a run used behind its last kernel).  In order: the launch
+  // counters (LaunchCtr and status word max_iters: the split epilogue's);
+  // the per-(tile, wave) counts (partsplit adds the fused children's up);
+  // the fused 2-means passes' arrival words per (iteration, record); the
+  // records' summaries (written as each becomes final: the next plan's
+  // scan); the partition's per-parent arrival words (split totals folded in).
+  struct RoundBlock {
+    size_t o_tiles, o_pt, o_extra, o_ctr, o_wp, o_rd, o_sum, o_sd, bytes;
+  };
+  static RoundBlock round_block(size_t nr, size_t tiles, size_t ptiles, size_t extra, int max_iters);
+  void round_args(Round& R, char* dblk, const RoundBlock& b, int mode);
   std::deque<Round> rounds_;          // (a deque: references stay valid while rounds are added)
   int wait_round_ = -1;               // the round finish_round waits on (diagnostics)
 
@@ -352,7 +374,6 @@ class Engine {
   void apply_tune(const char* spec);
   int src_fmt(const std::vector<int>& ids) const;
   void check_arena_zero(hipStream_t stream);
-  uint64_t tile_len_of(uint64_t len, uint64_t tl) const;
   uint64_t round_tile_len(uint64_t total) const;
   void replay(FrameState& f);
   void next_active(FrameState& f, std::vector<int>* active);

@@ -113,8 +113,8 @@ struct PlanArgs {
   const Tile* ptiles;       //                 tiles (the part tiles point into them)
   const int32_t* plist;     // parent (logical) nodes to split (host-coherent pinned memory)
   int32_t np;
-  int32_t node_tiles;       // tiles per record at least (Engine::tile_len)
-  uint32_t tl;              // tile length of the round (Engine::tile_len)
+  int32_t node_tiles;       // tiles per record at least (dq_rules.h, tile_len_of)
+  uint32_t tl;              // tile length of the round (Engine::round_tile_len)
   uint32_t tiles_cap, ptiles_cap;
   DevNode* cn;              // this round: 2 np records
   Tile* ct;

@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "dq_kernels.h"
+#include "dq_rules.h"
 #include "stl_order.h"
 
 namespace dq {
@@ -100,34 +101,27 @@ __device__ __forceinline__ void means_from_sums(const uint64_t t[F_NUM], double 
   *ow_out = ow;
 }
 
-// (:616-623) + the FP32 filter bound.  The filter evaluates
+// The FP64 decision (dq_rules.h, :616-623) + the FP32 filter bound.  The
+// filter evaluates
 //   df = rr*R + rg*G + rb*B - lhs   in f32 (3 fma).
-// With M = (|rr|+|rg|+|rb|)*255 + |lhs|, its error is below 7*2^-24*M (four
-// f32 conversions, three f32 roundings) and the FP64 sum's error is below
+// With M = decision_scale, its error is below 7*2^-24*M (four f32
+// conversions, three f32 roundings) and the FP64 sum's error is below
 // 4*2^-53*M, so whenever |df| > eps = 8e-7*M the sign of df equals the sign
 // of the FP64 expression's (lhs < sum) outcome.  Non-finite or tiny M
 // (NaN/inf means of an empty half) disables the filter: eps = +inf.
-__device__ __forceinline__ void decision_from_means(const double om[3], const double nm[3],
-                                                    Params* p) {
-  p->lhs = 0.5 * (om[0] * om[0] - nm[0] * nm[0] + om[1] * om[1] - nm[1] * nm[1] +
-                  om[2] * om[2] - nm[2] * nm[2]);
-  p->rr = om[0] - nm[0];
-  p->rg = om[1] - nm[1];
-  p->rb = om[2] - nm[2];
-  const double M = (fabs(p->rr) + fabs(p->rg) + fabs(p->rb)) * 255.0 + fabs(p->lhs);
-  p->lhsf = (float)p->lhs;
-  p->rrf = (float)p->rr;
-  p->rgf = (float)p->rg;
-  p->rbf = (float)p->rb;
+__device__ __forceinline__ void decision_with_filter(const double om[3], const double nm[3],
+                                                     Params* p) {
+  const Decision d = decision_from_means(om, nm);
+  p->lhs = d.lhs;
+  p->rr = d.rr;
+  p->rg = d.rg;
+  p->rb = d.rb;
+  const double M = decision_scale(d.lhs, d.rr, d.rg, d.rb);
+  p->lhsf = (float)d.lhs;
+  p->rrf = (float)d.rr;
+  p->rgf = (float)d.rg;
+  p->rbf = (float)d.rb;
   p->eps = (M > 1e-30 && M < 1e30) ? (float)(8e-7 * M) : __builtin_inff();
-}
-
-// Split pass threshold: cut_pos < v  <=>  v >= thr for integer v in [0,255].
-__device__ __forceinline__ int32_t split_threshold(double cut) {
-  if (!(cut == cut)) return 256;     // NaN: nothing moves
-  if (cut < 0.0) return 0;
-  if (cut >= 255.0) return 256;
-  return (int32_t)floor(cut) + 1;
 }
 
 
@@ -415,39 +409,6 @@ __device__ void node_results(NodeResult* r, const DevNode* w, const uint64_t t[F
   r->n_new = t[F_CNT];
 }
 
-// Is the first 2-means iteration after the split a fixed point, for every
-// point the node can hold?  p is that iteration's decision (old iff lhs <
-// rr*R + rg*G + rb*B, :683), the split sent v_axis >= thr new (:438-559).
-// On the node's box (w->box_lo/hi) the decision is checked at the corners of
-// both halves of the cut: every point with v_axis >= thr must go new (max of
-// the linear form <= lhs - margin) and every other point must stay old (min
-// >= lhs + margin).  The margin 1e-12*M dwarfs the FP64 evaluation's error
-// (< 4*2^-53*M, decision_from_means), so each point's exact outcome equals
-// the cut's.  Then the iteration's halves -- hence its exact integer sums --
-// are the split's, the next decision is p again, and the results are what
-// the first 2-means epilogue would publish as a fixed point.
-__device__ bool cut_is_fixed_point(const DevNode* w, const Params& p) {
-  const double M = (fabs(p.rr) + fabs(p.rg) + fabs(p.rb)) * 255.0 + fabs(p.lhs);
-  if (!(M > 1e-30 && M < 1e30)) return false;
-  const double mg = 1e-12 * M;
-  const double c[3] = {p.rr, p.rg, p.rb};
-  const int axis = (16 - p.shift) >> 3;
-  for (int side = 0; side < 2; ++side) {   // 0: the cut's old half, 1: its new half
-    int lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { lo[k] = w->box_lo[k]; hi[k] = w->box_hi[k]; }
-    if (side) lo[axis] = max(lo[axis], p.thr);
-    else hi[axis] = min(hi[axis], p.thr - 1);
-    if (lo[axis] > hi[axis]) continue;   // the box holds no point of this half
-    double ext = 0.0;
-    for (int k = 0; k < 3; ++k) {
-      const double a = c[k] * (double)lo[k], b = c[k] * (double)hi[k];
-      ext += side ? fmax(a, b) : fmin(a, b);
-    }
-    if (side ? !(ext <= p.lhs - mg) : !(ext >= p.lhs + mg)) return false;
-  }
-  return true;
-}
-
 // The FP64 update after pass KIND from the node's total sums t[] (exact
 // integers).  Publishes the next pass's Params, or -- when the results are
 // final (PASS_KLAST, or a PASS_KMEANS at a fixed point: prm then already
@@ -470,12 +431,9 @@ __device__ bool node_update(DevNode* w, NodeResult* r, const uint64_t t[F_NUM], 
       w->tm[c] = m;
       w->tv[c] = q;
     }
-    double maxv = tv[0], cut = tm[0];
-    int axis = 0;
-    if (maxv < tv[1]) { maxv = tv[1]; axis = 1; cut = tm[1]; }
-    if (maxv < tv[2]) { axis = 2; cut = tm[2]; }
-    w->prm.thr = split_threshold(cut);
-    w->prm.shift = 16 - 8 * axis;
+    const Cut cut = choose_cut(tm, tv);
+    w->prm.thr = split_threshold(cut.pos);
+    w->prm.shift = 16 - 8 * cut.axis;
     return false;
   }
   double tm[3];
@@ -496,9 +454,10 @@ __device__ bool node_update(DevNode* w, NodeResult* r, const uint64_t t[F_NUM], 
   }
   for (int c = 0; c < 4; ++c) w->prev[c] = t[F_CNT + c];
   Params p = w->prm;
-  decision_from_means(om, nm, &p);
+  decision_with_filter(om, nm, &p);
   w->prm = p;
-  if (KIND == PASS_SPLIT && fixed_point && t[F_CNT] != 0 && ow > 0.0 && cut_is_fixed_point(w, p)) {
+  if (KIND == PASS_SPLIT && fixed_point && t[F_CNT] != 0 && ow > 0.0 &&
+      cut_is_fixed_point(w->box_lo, w->box_hi, (16 - p.shift) >> 3, p.thr, p.lhs, p.rr, p.rg, p.rb)) {
     // exactly the first 2-means epilogue's fixed-point branch on sums t
     w->iter = 1;
     node_results(r, w, t, om, nm, nw, ow);
@@ -2197,62 +2156,24 @@ __global__ __launch_bounds__(kLoopBlock) void kloop_kernel(RoundArgs a, int32_t 
 
 // ---------------------------------------------------------------------------
 // Device-planned rounds (PlanArgs, dq_kernels.h).  The tables a host-built
-// round gets from Engine::run_round -- records, tiles, part tiles, cleared
-// counters -- built on the device from the previous round's records and
-// results, so the round can be enqueued before those results exist.  The
-// layout rules are Engine::tile_len and the record fill of run_round,
-// restated; the host mirrors them (Engine::mirror_planned) and checks the
-// counts.
-// Exact a / b for a < 2^22, b >= 1: a float reciprocal (error < 0.75 on the
-// quotient) and one correction each way.  (A generic 32-bit division is ~4x
-// the code; the sharded plan inlines 30+ of them and outgrew the I-cache.)
-__device__ __forceinline__ uint32_t small_udiv(uint32_t a, uint32_t b) {
-  uint32_t q = (uint32_t)((float)a * __builtin_amdgcn_rcpf((float)b));
-  int32_t r = (int32_t)(a - q * b);
-  if (r < 0) { q -= 1u; r += (int32_t)b; }
-  if ((uint32_t)r >= b) q += 1u;
-  return q;
-}
-
-// Tile length of a record of `len` points, in whole 4096-point sweeps:
-// Engine::tile_len_of (roundup_4096(ceil(len / nt)) clamped to [4096, tl])
-// restated on L = ceil(len / 4096) < 2^20 sweeps -- nested ceilings:
-// ceil(ceil(len / nt) / 4096) = ceil(L / nt).  tl is a whole number of sweeps
-// (round_tile_len, tile_max_), nt <= 65536 (apply_tune).
-static_assert(kSweep == 4096, "plan_tile_sweeps shifts by 12");
-__device__ __forceinline__ uint32_t plan_tile_sweeps(uint32_t len, uint32_t tl, int32_t nt) {
-  const uint32_t L = (len >> 12) + ((len & (kSweep - 1)) != 0 ? 1u : 0u);
-  const uint32_t m = small_udiv(L + (uint32_t)nt - 1u, (uint32_t)nt);
-  return max(1u, min(tl / kSweep, m));
-}
-
-__device__ __forceinline__ uint32_t plan_tile_len(uint32_t len, uint32_t tl, int32_t nt) {
-  return plan_tile_sweeps(len, tl, nt) * kSweep;
-}
-
-// ceil(len / tile length) = ceil(L / m) (nested ceilings again)
-__device__ __forceinline__ uint32_t plan_ntiles(uint32_t len, uint32_t tl, int32_t nt) {
-  if (len == 0) return 1;   // an empty record still gets one (empty) tile
-  const uint32_t L = (len >> 12) + ((len & (kSweep - 1)) != 0 ? 1u : 0u);
-  const uint32_t m = plan_tile_sweeps(len, tl, nt);
-  return small_udiv(L + m - 1u, m);
-}
+// round gets from Engine::enqueue_host_round -- records, tiles, part tiles,
+// cleared counters -- built on the device from the previous round's records
+// and results, so the round can be enqueued before those results exist.  The
+// record tiling is dq_rules.h's (tile_len_of, ntiles_of), the record fill
+// enqueue_host_round's; the host lays the same round out once its parents'
+// results exist (Engine::assign_planned) and checks the counts.
+static_assert(kSweep == (int)kTileSweep, "dq_rules.h tiles in the pass kernels' sweeps");
 
 // The split threshold / shift of a child (the cut of :388-403 from its mean
-// and variance), as plan_child and Engine::run_round.
+// and variance).
 __device__ __forceinline__ void plan_cut(const NodeResult& r, int side, int32_t* thr, int32_t* shift) {
-  const double* mean = side ? r.nm : r.om;
-  const double* var = side ? r.nv : r.ov;
-  double maxv = var[0], cut = mean[0];
-  int axis = 0;
-  if (maxv < var[1]) { maxv = var[1]; axis = 1; cut = mean[1]; }
-  if (maxv < var[2]) { axis = 2; cut = mean[2]; }
-  *thr = split_threshold(cut);
-  *shift = 16 - 8 * axis;
+  const Cut cut = choose_cut(side ? r.nm : r.om, side ? r.nv : r.ov);
+  *thr = split_threshold(cut.pos);
+  *shift = 16 - 8 * cut.axis;
 }
 
 // One child record: the parent's old (side 0) or new (side 1) half
-// (run_round's fill for a node fused into its parent's partition).
+// (enqueue_host_round's fill for a node fused into its parent's partition).
 // (Fields are stored one by one: a DevNode built in registers and copied as
 // a whole went through scratch memory.)
 __device__ void plan_child(const PlanArgs& a, const DevNode& P, const NodeResult& r, int side,
@@ -2278,8 +2199,8 @@ __device__ void plan_child(const PlanArgs& a, const DevNode& P, const NodeResult
   d->off = off;
   d->len = len;
   d->tile_begin = tb;
-  const uint32_t tln = plan_tile_len(len, a.tl, a.node_tiles);
-  d->tile_end = tb + (int32_t)plan_ntiles(len, a.tl, a.node_tiles);
+  const uint32_t tln = tile_len_of(len, a.tl, (uint32_t)a.node_tiles);
+  d->tile_end = tb + (int32_t)ntiles_of(len, a.tl, (uint32_t)a.node_tiles);
   d->split_pb = pb;
   d->split_pe = pe;
   d->split_side = side;
@@ -2292,15 +2213,11 @@ __device__ void plan_child(const PlanArgs& a, const DevNode& P, const NodeResult
   d->tv[0] = v0;
   d->tv[1] = v1;
   d->tv[2] = v2;
-  // the cut of :388-403 (plan_cut)
-  double maxv = v0, cut = m0;
-  int axis = 0;
-  if (maxv < v1) { maxv = v1; axis = 1; cut = m1; }
-  if (maxv < v2) { axis = 2; cut = m2; }
+  const Cut cut = choose_cut(m0, m1, m2, v0, v1, v2);   // (:388-403)
   d->prm.lhs = d->prm.rr = d->prm.rg = d->prm.rb = 0.0;
   d->prm.lhsf = d->prm.rrf = d->prm.rgf = d->prm.rbf = d->prm.eps = 0.0f;
-  d->prm.thr = split_threshold(cut);
-  d->prm.shift = 16 - 8 * axis;
+  d->prm.thr = split_threshold(cut.pos);
+  d->prm.shift = 16 - 8 * cut.axis;
   d->prm.pad = 0;
   for (int c = 0; c < 4; ++c) d->prev[c] = 0;
   d->n_new_local = 0;
@@ -2312,8 +2229,8 @@ __device__ void plan_child(const PlanArgs& a, const DevNode& P, const NodeResult
   // the box: the parent's, clipped at the parent's cut when its halves are the cut's
   for (int c = 0; c < 3; ++c) {
     if (proven && c == pax) {
-      if (side) lo[c] = max(lo[c], pthr);
-      else hi[c] = min(hi[c], pthr - 1);
+      if (side) lo[c] = clip_new_lo(lo[c], pthr);
+      else hi[c] = clip_old_hi(hi[c], pthr);
     }
     d->box_lo[c] = lo[c];
     d->box_hi[c] = hi[c];
@@ -2322,7 +2239,7 @@ __device__ void plan_child(const PlanArgs& a, const DevNode& P, const NodeResult
 
 // Plan + partition in one launch (one shard per node): the
 // planned round's part tile j is partitioned by workgroup j right after
-// plan_kernel's bookkeeping, restated per workgroup -- every workgroup scans
+// plan_kernel's bookkeeping, repeated by every workgroup -- every workgroup scans
 // all parents (abort check, the tile counts' exclusive bases), finds the
 // parent of part tile j, and the workgroup of a parent's FIRST part tile
 // writes the parent's two child records and their tiles (read by the next
@@ -2346,7 +2263,7 @@ __device__ __forceinline__ void plansplit_body(const PlanArgs& pa, const RoundAr
   const int32_t np = pa.np;
   const uint32_t j = blockIdx.x;
   auto parent = [&](int32_t i) -> int32_t { return pa.plist ? pa.plist[i] : i; };
-  auto ntl = [&](uint32_t len) { return plan_ntiles(len, pa.tl, pa.node_tiles); };
+  auto ntl = [&](uint32_t len) { return ntiles_of(len, pa.tl, (uint32_t)pa.node_tiles); };
   if (tid == 0) {
     s_abort = 0;
     s_par = -1;
@@ -2423,7 +2340,7 @@ __device__ __forceinline__ void plansplit_body(const PlanArgs& pa, const RoundAr
   if (j == pb) {   // the parent's first part tile: its children's records and tiles
     if (tid == 0) plan_child(pa, *Pp, *rp, 0, 2 * i, off, lo, (int32_t)cb, (int32_t)pb, pe);
     if (tid == 64) plan_child(pa, *Pp, *rp, 1, 2 * i + 1, off + lo, nn, (int32_t)(cb + nto), (int32_t)pb, pe);
-    const uint32_t tlo = plan_tile_len(lo, pa.tl, pa.node_tiles), tln = plan_tile_len(nn, pa.tl, pa.node_tiles);
+    const uint32_t tlo = tile_len_of(lo, pa.tl, (uint32_t)pa.node_tiles), tln = tile_len_of(nn, pa.tl, (uint32_t)pa.node_tiles);
     for (uint32_t k = tid; k < nto + ntn; k += kBlock) {
       const int side = k < nto ? 0 : 1;
       const uint32_t kk = side ? k - nto : k;
@@ -2452,11 +2369,11 @@ __device__ __forceinline__ void plansplit_body(const PlanArgs& pa, const RoundAr
   ci0.on = ci1.on = 1;
   ci0.off = off;
   ci0.len = lo;
-  ci0.tl = plan_tile_len(lo, pa.tl, pa.node_tiles);
+  ci0.tl = tile_len_of(lo, pa.tl, (uint32_t)pa.node_tiles);
   ci0.tb = cb;
   ci1.off = off + lo;
   ci1.len = nn;
-  ci1.tl = plan_tile_len(nn, pa.tl, pa.node_tiles);
+  ci1.tl = tile_len_of(nn, pa.tl, (uint32_t)pa.node_tiles);
   ci1.tb = cb + nto;
   for (ChildInfo* c : {&ci0, &ci1}) {   // (the tile lengths: VALU divisions)
     c->tl = __builtin_amdgcn_readfirstlane(c->tl);
@@ -2507,7 +2424,7 @@ __global__ __launch_bounds__(kPlanBlock) void plan_kernel(PlanArgs a, uint32_t n
   const uint32_t tid = threadIdx.x, lane = lane_id(), wv = wave_id();
   const int32_t np = a.np, S = a.nshard;
   auto parent = [&](int32_t i) -> int32_t { return a.plist ? a.plist[i] : i; };   // logical, in prev
-  auto ntl = [&](uint32_t len) { return plan_ntiles(len, a.tl, a.node_tiles); };
+  auto ntl = [&](uint32_t len) { return ntiles_of(len, a.tl, (uint32_t)a.node_tiles); };
   if (tid == 0) s_abort = 0;
   __syncthreads();   // (the round's [LaunchCtr | wparts | rdone | summaries] are zero on entry: plansplit_body)
   // (1) every parent final? exclusive scans of the tile counts, chunk by
@@ -2652,7 +2569,7 @@ __global__ __launch_bounds__(kPlanBlock) void plan_kernel(PlanArgs a, uint32_t n
         k -= nt;
       }
     }
-    const uint32_t tln = plan_tile_len(len, a.tl, a.node_tiles);
+    const uint32_t tln = tile_len_of(len, a.tl, (uint32_t)a.node_tiles);
     Tile* tt = a.ct + j;
     tt->node = (2 * i + side) * S + sh;
     tt->start = off + k * tln;

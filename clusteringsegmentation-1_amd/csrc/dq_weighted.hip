@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
+#include "dq_rules.h"
 #include "dq_weighted.h"
 
 namespace dq {
@@ -841,53 +842,24 @@ __device__ void w_apply_tile(const WArgs& a, const WState& st, int ti, int pass,
 }
 
 __device__ void w_cut(WState& w, const double tm[3], const double tv[3]) {   // :388-403
-  double maxv = tv[0], cut = tm[0];
-  int axis = 0;
-  if (maxv < tv[1]) { maxv = tv[1]; axis = 1; cut = tm[1]; }
-  if (maxv < tv[2]) { axis = 2; cut = tm[2]; }
-  w.axis = axis;
-  w.cut = cut;
-}
-
-__device__ int32_t w_threshold(double cut) {   // cut < v <=> v >= thr (integer v in [0, 255])
-  if (!(cut == cut)) return 256;
-  if (cut < 0.0) return 0;
-  if (cut >= 255.0) return 256;
-  return (int32_t)floor(cut) + 1;
+  const Cut cut = choose_cut(tm, tv);
+  w.axis = cut.axis;
+  w.cut = cut.pos;
 }
 
 // The first 2-means decision after the split keeps every point of the node's
-// box on its side of the cut (dq_kernels.hip cut_is_fixed_point, the same
-// corner test and margin): the first 2-means pass then folds exactly the
-// split's summands and is a fixed point.
+// box on its side of the cut (dq_rules.h): the first 2-means pass then folds
+// exactly the split's summands and is a fixed point.
 __device__ bool w_cut_is_fixed_point(const WState& w) {
-  const double M = (fabs(w.rr) + fabs(w.rg) + fabs(w.rb)) * 255.0 + fabs(w.lhs);
-  if (!(M > 1e-30 && M < 1e30)) return false;
-  const double mg = 1e-12 * M;
-  const double c[3] = {w.rr, w.rg, w.rb};
-  const int thr = w_threshold(w.cut);
-  for (int side = 0; side < 2; ++side) {
-    int lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { lo[k] = w.box_lo[k]; hi[k] = w.box_hi[k]; }
-    if (side) lo[w.axis] = max(lo[w.axis], thr);
-    else hi[w.axis] = min(hi[w.axis], thr - 1);
-    if (lo[w.axis] > hi[w.axis]) continue;
-    double ext = 0.0;
-    for (int k = 0; k < 3; ++k) {
-      const double x = c[k] * (double)lo[k], y = c[k] * (double)hi[k];
-      ext += side ? fmax(x, y) : fmin(x, y);
-    }
-    if (side ? !(ext <= w.lhs - mg) : !(ext >= w.lhs + mg)) return false;
-  }
-  return true;
+  return cut_is_fixed_point(w.box_lo, w.box_hi, w.axis, split_threshold(w.cut), w.lhs, w.rr, w.rg, w.rb);
 }
 
 __device__ void w_decision(WState& w) {   // :616-623
-  w.lhs = 0.5 * (w.om[0] * w.om[0] - w.nm[0] * w.nm[0] + w.om[1] * w.om[1] - w.nm[1] * w.nm[1] +
-                 w.om[2] * w.om[2] - w.nm[2] * w.nm[2]);
-  w.rr = w.om[0] - w.nm[0];
-  w.rg = w.om[1] - w.nm[1];
-  w.rb = w.om[2] - w.nm[2];
+  const Decision d = decision_from_means(w.om, w.nm);
+  w.lhs = d.lhs;
+  w.rr = d.rr;
+  w.rg = d.rg;
+  w.rb = d.rb;
 }
 
 // Pass step 4: per node (one wave), the folds in sequence order -- tiles in

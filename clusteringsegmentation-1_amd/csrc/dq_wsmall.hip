@@ -140,6 +140,10 @@ __device__ __forceinline__ int64_t ws_readlane_i64(int64_t v, int l) {
 }
 __device__ __forceinline__ int64_t ws_wave_sum_i64(int64_t v) { return ws_readlane_i64(ws_wave_scan_i64(v), 63); }
 
+// This file keeps its own statements of dq_rules.h's threshold, corner test,
+// decision, cut and box clip -- operation for operation the same, keep them
+// so: built on the shared ones the region calls measured 1-4 % slower
+// (10^4 points: 183.3 -> 185.1 us; one latency-bound workgroup).
 __device__ __forceinline__ int32_t ws_threshold(double cut) {   // cut < v <=> v >= thr
   if (!(cut == cut)) return 256;
   if (cut < 0.0) return 0;

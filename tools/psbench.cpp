@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "dq_kernels.h"
+#include "dq_rules.h"
 
 using namespace dq;
 
@@ -119,22 +120,17 @@ static bool stays_old(const DevNode& p, uint8_t r, uint8_t g, uint8_t b) {
 }
 
 static void set_plane(Params& q, const double om[3], const double nm[3]) {
-  q.lhs = 0.5 * (om[0] * om[0] - nm[0] * nm[0] + om[1] * om[1] - nm[1] * nm[1] + om[2] * om[2] - nm[2] * nm[2]);
-  q.rr = om[0] - nm[0];
-  q.rg = om[1] - nm[1];
-  q.rb = om[2] - nm[2];
-  const double M = (fabs(q.rr) + fabs(q.rg) + fabs(q.rb)) * 255.0 + fabs(q.lhs);
+  const Decision d = decision_from_means(om, nm);
+  q.lhs = d.lhs;
+  q.rr = d.rr;
+  q.rg = d.rg;
+  q.rb = d.rb;
+  const double M = decision_scale(d.lhs, d.rr, d.rg, d.rb);
   q.lhsf = (float)q.lhs;
   q.rrf = (float)q.rr;
   q.rgf = (float)q.rg;
   q.rbf = (float)q.rb;
   q.eps = (float)(8e-7 * M);
-}
-
-static uint32_t tile_len_of(uint32_t len, uint32_t tl, int nt) {
-  uint64_t t = (len + nt - 1) / nt;
-  t = ((t + kSweep - 1) / kSweep) * kSweep;
-  return (uint32_t)std::max<uint64_t>(kSweep, std::min<uint64_t>(tl, t));
 }
 
 static void wave_range(uint32_t start, uint32_t end, uint32_t w, uint32_t& ws, uint32_t& we) {
@@ -285,7 +281,7 @@ int main(int argc, char** argv) {
           c.len = s ? par[i].n_new_local : pnold[i];
           c.tile_len = tile_len_of(c.len, round_tl, 8);
           c.tile_begin = (int32_t)ctiles;
-          const uint32_t nt = c.len == 0 ? 1u : (c.len + c.tile_len - 1) / c.tile_len;
+          const uint32_t nt = ntiles_of(c.len, round_tl, 8);
           c.tile_end = (int32_t)(ctiles + nt);
           ctb[2 * i + s] = ctiles;
           ctiles += nt;
