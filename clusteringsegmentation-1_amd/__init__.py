@@ -15,6 +15,8 @@ Reference-named entry points (same argument meaning, host numpy arrays):
     quant_varpart_fast(pixels, num_clusters, max_iters=10)   -> colortable
 Device-resident entry points (torch tensors / raw device pointers on HBM):
     quant_device, quant_batch_device, cluster_device, map_device
+Cluster labels (each pixel's index into the colortable, u8 / u16 / u32):
+    map_labels_device, quant_labels_batch_device, quant_labels
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -77,6 +79,10 @@ def lib():
         "dq_hip_comm_size": ([c.c_int], c.c_int),
         "dq_hip_cluster_dev": ([c.c_int, vp, c.c_uint32, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_map_dev": ([c.c_int, vp, c.c_uint32, vp, vp, c.c_int, vp], c.c_int),
+        "dq_hip_map_labels_dev": ([c.c_int, vp, c.c_uint32, vp, c.c_int, vp, c.c_int, vp], c.c_int),
+        "dq_hip_quant_labels_batch_dev": ([c.c_int, c.c_int, vp, vp, vp, c.c_int, c.c_uint32, vp, vp, c.c_int,
+                                           c.c_int, vp], c.c_int),
+        "dq_hip_quant_labels": ([vp, c.c_uint32, vp, c.c_int, u32p, vp, c.c_int], c.c_int),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -469,6 +475,91 @@ def map_device(t_in, t_out, colortable, device=0, n=None, stream=None):
     if lib().dq_hip_map_dev(device, _dptr(t_in), n, _dptr(t_out), _ptr(ct), ct.size,
                             _stream_ptr(stream)) < 0:
         raise DivQuantError("dq_hip_map_dev: bad arguments")
+
+
+# ---------------------------------------------------------------------------
+# Cluster labels: each pixel's index into the colortable instead of its mapped
+# colour (include/dq_hip.h: the lowest i with ct[i] == the mapped colour).  The
+# label width is the label tensor's element size: 1, 2 or 4 bytes (uint8,
+# uint16 / int16, uint32 / int32 storage).
+def _label_width(t, n, what="t_labels"):
+    """Element size of a label tensor (torch tensor or numpy array) after the
+    checks every label entry point makes before it calls the library."""
+    if isinstance(t, np.ndarray):
+        size, contiguous, count = t.itemsize, t.flags.c_contiguous, t.size
+    elif hasattr(t, "element_size"):
+        size, contiguous, count = t.element_size(), t.is_contiguous(), t.numel()
+    else:
+        raise ValueError("%s: a tensor or an array (its element size is the label width)" % what)
+    if size not in (1, 2, 4):
+        raise ValueError("%s: labels are 1, 2 or 4 bytes wide, not %d" % (what, size))
+    if not contiguous:
+        raise ValueError("%s is not contiguous" % what)
+    if count < n:
+        raise ValueError("%s holds %d labels, the input has %d pixels" % (what, count, n))
+    return size
+
+
+def map_labels_device(t_in, t_labels, colortable, device=0, n=None, stream=None):
+    """The cluster label of each of n device-resident pixels: the lowest index
+    i with colortable[i] == the colour map_device writes for the pixel.
+    t_labels: a contiguous device tensor of at least n elements of 1, 2 or 4
+    bytes (the width must hold len(colortable) - 1).  ValueError for a bad
+    label tensor (nothing runs), DivQuantError when the library refuses."""
+    n = _nelem(t_in, n)
+    width = _label_width(t_labels, n)
+    ct = _u32(colortable).reshape(-1)
+    if lib().dq_hip_map_labels_dev(device, _dptr(t_in), n, _dptr(t_labels), width, _ptr(ct), ct.size,
+                                   _stream_ptr(stream)) < 0:
+        raise DivQuantError("dq_hip_map_labels_dev: bad arguments")
+
+
+def quant_labels_batch_device(t_ins, t_labels, num_clusters, all_pixels_unique=1, max_iters=10, device=0,
+                              stream=None):
+    """quant_batch_device with labels in place of colours: frame i's labels
+    (t_labels[i], one width for the whole batch) index its deduplicated
+    colortable.  all_pixels_unique=0: every frame through the weighted path.
+    Returns ([colortable per frame], total_empty)."""
+    nf = len(t_ins)
+    if len(t_labels) != nf:
+        raise ValueError("%d label tensors for %d frames" % (len(t_labels), nf))
+    widths = {_label_width(t, ti.numel(), "t_labels[%d]" % i) for i, (t, ti) in enumerate(zip(t_labels, t_ins))}
+    if len(widths) > 1:
+        raise ValueError("the label tensors of a batch must have one element size")
+    if nf == 0:
+        raise ValueError("empty batch")
+    ins = (ctypes.c_void_p * nf)(*[_dptr(t).value for t in t_ins])
+    labs = (ctypes.c_void_p * nf)(*[_dptr(t).value for t in t_labels])
+    ns = np.array([t.numel() for t in t_ins], np.uint32)
+    ct = np.zeros((nf, num_clusters), np.uint32)
+    kout = np.zeros(nf, np.uint32)
+    r = lib().dq_hip_quant_labels_batch_dev(device, nf, ctypes.cast(ins, ctypes.c_void_p), _ptr(ns),
+                                            ctypes.cast(labs, ctypes.c_void_p), widths.pop(), num_clusters,
+                                            _ptr(ct), _ptr(kout), int(all_pixels_unique), max_iters,
+                                            _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_quant_labels_batch_dev: bad arguments")
+    return [ct[i, :kout[i]].copy() for i in range(nf)], r
+
+
+def quant_labels(pixels, num_clusters, all_pixels_unique=1, dtype=None):
+    """quant_recurse of host pixels returning (labels, colortable): labels[i]
+    is pixel i's index into the (deduplicated) colortable.  dtype: uint8,
+    uint16 or uint32 (None: the narrowest that holds num_clusters - 1)."""
+    if dtype is None:
+        dtype = np.uint8 if num_clusters <= 256 else np.uint16 if num_clusters <= 65536 else np.uint32
+    dtype = np.dtype(dtype)
+    if dtype.itemsize not in (1, 2, 4) or dtype.kind not in "ui":
+        raise ValueError("labels are 1-, 2- or 4-byte integers, not %s" % dtype)
+    _require_gpu()
+    px = _u32(pixels).reshape(-1)
+    labels = np.zeros(px.size, dtype)
+    ct = np.zeros(max(int(num_clusters), 1), np.uint32)
+    k = ctypes.c_uint32(max(int(num_clusters), 0))
+    if lib().dq_hip_quant_labels(_ptr(px), px.size, _ptr(labels), dtype.itemsize, ctypes.byref(k), _ptr(ct),
+                                 int(all_pixels_unique)) < 0:
+        raise DivQuantError("dq_hip_quant_labels: bad arguments")
+    return labels, ct[:k.value].copy()
 
 
 # ---------------------------------------------------------------------------

@@ -26,7 +26,6 @@
 #include <cstring>
 #include <iostream>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/DivQuantHeader.h"
@@ -116,19 +115,12 @@ bool clusteringCombine(const dqcli::Image& input, dqcli::Image* result) {
   quant_recurse(n, in.data(), out.data(), &k, colortable.data(), 0);
   cout << "quant_recurse K=" << kreq << " -> " << k << " colours" << endl;
 
-  // tags: a pixel's index in the (deduplicated) colortable
-  unordered_map<uint32_t, uint32_t> tag_of;
-  for (uint32_t i = 0; i < k; ++i) tag_of.emplace(colortable[i], i);
-  vector<uint32_t> tags(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    auto it = tag_of.find(out[i]);
-    if (it == tag_of.end()) {
-      cerr << "mapped colour 0x" << hex << out[i] << dec << " is not in the colortable" << endl;
-      return false;
-    }
-    tags[i] = it->second;
+  // tags: a pixel's index in the (deduplicated) colortable -- its cluster
+  // label, as u32, mapped on the GPU from the pixels still resident there
+  if (dq_hip_map_labels_dev(dev, d_px, n, d_quant, 4, colortable.data(), (int)k, nullptr) != 0) {
+    cerr << "label map failed" << endl;
+    return false;
   }
-  hip_check(hipMemcpy(d_quant, tags.data(), (size_t)n * 4, hipMemcpyHostToDevice), "hipMemcpy");
   if (!unpack_to_image(dev, d_quant, width, height, result)) return false;
   for (void* p : {(void*)d_bgr, (void*)d_px, (void*)d_quant, (void*)d_mode}) hip_check(hipFree(p), "hipFree");
   return true;

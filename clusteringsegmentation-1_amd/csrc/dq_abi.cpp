@@ -791,6 +791,80 @@ int dq_hip_map(const uint32_t* in, uint32_t n, uint32_t* out, const uint32_t* ct
   return 0;
 }
 
+// Cluster labels (u8 / u16 / u32 label maps).  A width that cannot hold index
+// k - 1 is a bad argument: checked, like everything else, before any HIP call.
+static bool label_width_ok(int label_bytes, uint64_t k) {
+  if (label_bytes != 1 && label_bytes != 2 && label_bytes != 4) return false;
+  return k >= 1 && k - 1 <= (label_bytes == 4 ? 0xFFFFFFFFull : (1ull << (8 * label_bytes)) - 1);
+}
+
+int dq_hip_map_labels_dev(int device, const uint32_t* d_in, uint32_t n, void* d_labels,
+                          int label_bytes, const uint32_t* ct, int k, void* stream) {
+  if (!d_in || !d_labels || !ct || k <= 0 || !label_width_ok(label_bytes, (uint64_t)k)) return -1;
+  if (((uintptr_t)d_labels & (uintptr_t)(label_bytes - 1)) != 0) return -1;
+  if (n == 0) return 0;
+  Engine& e = engine_for(device);
+  std::lock_guard<std::mutex> g(e.mutex());
+  e.map_labels(d_in, n, d_labels, label_bytes, ct, k, dev_stream(e, stream));
+  return 0;
+}
+
+int dq_hip_quant_labels_batch_dev(int device, int nframes, const uint32_t* const* d_in,
+                                  const uint32_t* n, void* const* d_labels, int label_bytes,
+                                  uint32_t k, uint32_t* ct, uint32_t* k_out, int uniq,
+                                  int max_iters, void* stream) {
+  if (nframes <= 0 || !d_in || !n || !d_labels || !ct || !k_out || k == 0 || max_iters < 1 ||
+      !label_width_ok(label_bytes, k))
+    return -1;
+  for (int i = 0; i < nframes; ++i)
+    if (!d_in[i] || !d_labels[i] || n[i] == 0 || ((uintptr_t)d_labels[i] & (uintptr_t)(label_bytes - 1)) != 0)
+      return -1;
+  std::vector<dq::FrameJob> jobs(nframes);
+  for (int i = 0; i < nframes; ++i) {
+    jobs[i].d_in = d_in[i];
+    jobs[i].n = n[i];
+    jobs[i].d_labels = d_labels[i];
+    jobs[i].label_bytes = label_bytes;
+    jobs[i].k = (int)k;
+    jobs[i].ct = ct + (size_t)i * k;
+  }
+  int empty = 0;
+  if (uniq) {
+    empty = quant_batch(device, jobs, max_iters, stream);
+  } else {   // the weighted path, one frame after the other (as dq_hip_quant_weighted_dev)
+    Engine& e = engine_for(device);
+    std::lock_guard<std::mutex> g(e.mutex());
+    for (int i = 0; i < nframes; ++i) {
+      e.run_weighted(jobs[i], max_iters, true, dev_stream(e, stream));
+      empty += jobs[i].num_empty;
+    }
+  }
+  for (int i = 0; i < nframes; ++i) k_out[i] = (uint32_t)jobs[i].k_out;
+  return empty;
+}
+
+int dq_hip_quant_labels(const uint32_t* in, uint32_t n, void* labels, int label_bytes,
+                        uint32_t* k, uint32_t* ct, int uniq) {
+  if (!in || !labels || !k || !ct || n == 0 || *k == 0 || !label_width_ok(label_bytes, *k)) return -1;
+  Engine& e = engine_for(current_device());
+  std::lock_guard<std::mutex> g(e.mutex());
+  hipStream_t st = e.stream();
+  e.stage_in(in, n, st);
+  dq::FrameJob j;
+  j.d_in = e.staged_in();
+  j.n = n;
+  j.d_labels = e.staged_out();   // (n words: room for n labels of any width)
+  j.label_bytes = label_bytes;
+  j.k = (int)*k;
+  j.ct = ct;
+  if (uniq) e.run(&j, 1, 10, true, st);
+  else e.run_weighted(j, 10, true, st);
+  DQ_HIP(hipMemcpyAsync(labels, e.staged_out(), (size_t)n * (size_t)label_bytes, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  *k = (uint32_t)j.k_out;
+  return j.num_empty;
+}
+
 // Synthetic frames of the benchmark configs (SURVEY 8c/8d generator) and the
 // output checksum the golden fixtures are keyed by.
 void dq_synth_xorshift(uint32_t* out, uint64_t n, uint64_t seed) {

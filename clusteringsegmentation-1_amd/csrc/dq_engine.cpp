@@ -17,6 +17,7 @@
 #include <deque>
 #include <functional>
 #include <string>
+#include <unordered_map>
 
 namespace dq {
 
@@ -1476,6 +1477,8 @@ void Engine::run(FrameJob* jobs, int nframes, int max_iters, bool dedup_map,
     DQ_CHECK(j.n_global == 0 || j.n_global == j.n || cross_process(),
              "n_global > n needs a communicator (dq_hip_comm_init)");
     DQ_CHECK(!j.bgr || (S == 1 && (j.n_global == 0 || j.n_global == j.n)), "BGR24 frames are one shard");
+    DQ_CHECK(!j.d_labels || (S == 1 && !j.bgr && (j.n_global == 0 || j.n_global == j.n)),
+             "labels are for whole packed frames of one process");
     FrameState& f = frames_[i];
     f.job = &j;
     // shard boundaries: whole rows when the width is known, else 4-point multiples
@@ -1653,6 +1656,12 @@ void Engine::run(FrameJob* jobs, int nframes, int max_iters, bool dedup_map,
       if (j.d_out)   // every shard's rows with the frame's palette
         for (int sh = 0; sh < S; ++sh)
           if (f.n[sh] > 0) mj.push_back(MapJob{f.in[sh], f.n[sh], j.d_out + f.first[sh], j.ct, m, j.bgr});
+      if (j.d_labels) {   // (whole packed frames: checked on entry)
+        MapJob lj{j.d_in, j.n, nullptr, j.ct, m};
+        lj.d_labels = j.d_labels;
+        lj.label_bytes = j.label_bytes;
+        mj.push_back(lj);
+      }
     }
     if (!mj.empty()) map_many(mj.data(), (int)mj.size(), stream, false);
     tmark("map:enqueued");
@@ -1990,6 +1999,7 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
     const int m = dedup_colortable(job.ct, job.k_out, table);
     job.k_out = m;
     if (job.d_out) map(job.d_in, job.n, job.d_out, job.ct, m, stream);
+    if (job.d_labels) map_labels(job.d_in, job.n, job.d_labels, job.label_bytes, job.ct, m, stream);
   }
   DQ_HIP(hipStreamSynchronize(stream));
 }
@@ -2046,6 +2056,8 @@ bool Engine::run_weighted_small(FrameJob& job, int max_iters, bool dedup_map, hi
     DQ_CHECK(m == (int)r.m, "small weighted kernel: dedup count differs from the host's");
     job.k_out = m;
     if (job.d_out && !r.mapped) map(job.d_in, job.n, job.d_out, job.ct, m, stream);
+    // (labels: the kernel clusters and dedups, the map kernels label)
+    if (job.d_labels) map_labels(job.d_in, job.n, job.d_labels, job.label_bytes, job.ct, m, stream);
   }
   return true;
 }
@@ -2279,11 +2291,20 @@ void sorted_palette(const uint32_t* ct, int k, uint32_t* pal_out, uint16_t* lut_
   for (int v = 0; v < 766; ++v) lut_out[v] = (uint16_t)lut[v];
 }
 
+// A label map's table: sorted-palette index -> label, the lowest caller index
+// holding that colour (low 24 bits; unique for a deduplicated colortable).
+void label_table(const uint32_t* ct, int k, const uint32_t* sorted, uint16_t* lab) {
+  std::unordered_map<uint32_t, uint16_t> lowest;
+  lowest.reserve((size_t)k * 2);
+  for (int i = 0; i < k; ++i) lowest.emplace(ct[i] & 0xFFFFFFu, (uint16_t)i);   // (keeps the first)
+  for (int x = 0; x < k; ++x) lab[x] = lowest.find(sorted[x])->second;
+}
+
 // Per-map block of the map staging: [LUT: 768 u16 | palette: k words,
-// padded to 16 B], blocks packed; the staging starts with the MapTask table
-// of the launch.
+// padded to 16 B | label maps: k u16 labels, padded to 16 B], blocks packed;
+// the staging starts with the MapTask table of the launch.
 constexpr size_t kMapPal = 16384;
-constexpr size_t kMapBlockWords = kMapPal + 768 / 2;
+constexpr size_t kMapBlockWords = kMapPal + 768 / 2 + kMapPal / 2;
 constexpr int kMapChunk = 16;   // tasks per batched launch (cell tables: 2.5 MB each)
 }  // namespace
 
@@ -2313,7 +2334,36 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
   for (int i = 0; i < njobs; ++i) {
     DQ_CHECK(jobs[i].k > 0, "colormapSize must be > 0 (DivQuantMapColors.cpp:264)");
     DQ_CHECK(jobs[i].k <= (int)kMapPal, "colormapSize > 16384 is not supported by the LDS palette");
+    if (jobs[i].d_labels) {
+      const int lb = jobs[i].label_bytes;
+      DQ_CHECK(lb == 1 || lb == 2 || lb == 4, "label_bytes must be 1, 2 or 4");
+      DQ_CHECK(lb == 4 || (uint32_t)(jobs[i].k - 1) < (1u << (8 * lb)), "the label width cannot hold index k - 1");
+      DQ_CHECK(!jobs[i].bgr, "label maps read packed pixels");
+      DQ_CHECK(((uintptr_t)jobs[i].d_labels & (uintptr_t)(lb - 1)) == 0, "label pointer not naturally aligned");
+    }
   }
+  auto fmt_of = [](const MapJob& j) { return j.d_labels ? j.label_bytes : 0; };
+  // the destination: colours or labels
+  auto dst_of = [](const MapJob& j) -> const void* { return j.d_labels ? j.d_labels : (const void*)j.d_out; };
+  // One launch maps one output format: jobs of several formats go format by
+  // format (colour jobs and label jobs never share a cell table either)
+  {
+    bool mixed = false;
+    for (int i = 1; i < njobs; ++i) mixed |= fmt_of(jobs[i]) != fmt_of(jobs[0]);
+    if (mixed) {
+      for (int fmt : {0, 1, 2, 4}) {
+        std::vector<MapJob> part;
+        for (int i = 0; i < njobs; ++i)
+          if (fmt_of(jobs[i]) == fmt) part.push_back(jobs[i]);
+        if (!part.empty()) map_many(part.data(), (int)part.size(), stream, false);
+      }
+      if (!sync) return;
+      sync_stream(stream);
+      collect_timing();
+      return;
+    }
+  }
+  const int lb = njobs > 0 ? fmt_of(jobs[0]) : 0;   // this call's label width (0: colours)
   // A task maps at most kMapTaskMax pixels: map_lds_kernel stores through a
   // buffer resource whose byte range (4 n) must stay below 2^31.  Larger jobs
   // become consecutive tasks over the same colortable (they then share one
@@ -2330,6 +2380,7 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
           j.d_in = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(jobs[i].d_in) +
                                                      (size_t)o * (jobs[i].bgr ? 3 : 4));
           j.d_out = jobs[i].d_out + o;
+          if (j.d_labels) j.d_labels = reinterpret_cast<uint8_t*>(jobs[i].d_labels) + (size_t)o * (size_t)lb;
           split.push_back(j);
         }
       jobs = split.data();
@@ -2347,7 +2398,7 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
       kmax_all = std::max(kmax_all, jobs[i].k);
       any_bgr |= jobs[i].bgr;
       all_bgr &= jobs[i].bgr;
-      any_staged |= !jobs[i].bgr && (((uintptr_t)jobs[i].d_in & 15) != 0 || ((uintptr_t)jobs[i].d_out & 15) != 0);
+      any_staged |= !jobs[i].bgr && (((uintptr_t)jobs[i].d_in & 15) != 0 || ((uintptr_t)dst_of(jobs[i]) & 15) != 0);
     }
     if (any_bgr) {
       size_t need = 0;
@@ -2418,8 +2469,8 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
     }
     // K <= 1024: the LDS-table map, one workgroup per CU over all tasks
     const bool lds_map = kmax <= 1024 && use_lds_map_;
-    auto misaligned = [](const MapJob& j) {
-      return !j.bgr && (((uintptr_t)j.d_in & 15) != 0 || ((uintptr_t)j.d_out & 15) != 0);
+    auto misaligned = [&](const MapJob& j) {
+      return !j.bgr && (((uintptr_t)j.d_in & 15) != 0 || ((uintptr_t)dst_of(j) & 15) != 0);
     };
     // Tasks with the same colortable (a frame's row shards) share one palette
     // block and one cell table: the table lists the first of each colortable
@@ -2455,11 +2506,14 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
         m.cell_c32 = f.cell_c32;
       } else {
         blk_off[x] = woff;
-        blk_words[x] = 768 / 2 + (((size_t)j.k + 3) & ~(size_t)3);
+        blk_words[x] = 768 / 2 + map_label_off((uint32_t)j.k) + (lb ? (((size_t)j.k + 7) & ~(size_t)7) / 2 : 0);
         woff += blk_words[x];
         uint32_t* hb = hblk0 + blk_off[x];
         const uint32_t* db = dblk0 + blk_off[x];
         sorted_palette(j.ct, j.k, hb + 768 / 2, reinterpret_cast<uint16_t*>(hb));
+        if (lb)
+          label_table(j.ct, j.k, hb + 768 / 2,
+                      reinterpret_cast<uint16_t*>(hb + 768 / 2 + map_label_off((uint32_t)j.k)));
         m.pal = db + 768 / 2;
         m.lut = reinterpret_cast<const uint16_t*>(db);
         m.cell_rec = d_cell_rec_ + (size_t)x * kCells * kCellRecWords;
@@ -2467,7 +2521,8 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
         m.cell_c32 = d_cell_c32_ + (size_t)x * kCells;
       }
       m.in = j.d_in;
-      m.out = j.d_out;
+      m.out = lb ? reinterpret_cast<uint32_t*>(j.d_labels) : j.d_out;
+      m.labels = lb;
       m.bgr = j.bgr ? 1 : 0;   // (aligned and K <= 1024: never staged)
       if (misaligned(j)) staged.push_back(x);   // (identity order)
       m.n = j.n;
@@ -2502,14 +2557,14 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
       DQ_HIP(hipGetLastError());   // (a rejected launch would leave the output as it was)
       timed_end(ST_CELLS, 0.0, stream);
       // (the staging-reuse event behind the map's kernels, as for round tables)
-      double px = 0, mb = 0;   // pixels; bytes: 4 (BGR24: 3) read + 4 written per pixel
+      double px = 0, mb = 0;   // pixels; bytes: 4 (BGR24: 3) read + 4 (labels: their width) written per pixel
       for (int t = 0; t < nt; ++t) {
         px += ht[t].n;
-        mb += (ht[t].bgr ? 7.0 : 8.0) * ht[t].n;
+        mb += (lb ? 4.0 + lb : ht[t].bgr ? 7.0 : 8.0) * ht[t].n;
       }
       timed_begin(stream);
-      if (lds_map) launch_map_lds(dt, nt, kmax, nblocks, ht[0].bgr != 0, stream);
-      else launch_map(dt, nt, kmax, nblocks, stream);
+      if (lds_map) launch_map_lds(dt, nt, kmax, nblocks, ht[0].bgr != 0, stream, lb);
+      else launch_map(dt, nt, kmax, nblocks, stream, lb);
       DQ_HIP(hipGetLastError());
       timed_end(ST_MAP, mb, stream, px);
       DQ_HIP(hipEventRecord(map_ev_, stream));
@@ -2519,7 +2574,7 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
       for (int t = 0; t < nt; ++t) {
         const MapJob& j = jobs[c0 + t];
         MapTask one = ht[t];
-        const bool st = ((uintptr_t)j.d_in & 15) != 0 || ((uintptr_t)j.d_out & 15) != 0;
+        const bool st = ((uintptr_t)j.d_in & 15) != 0 || ((uintptr_t)dst_of(j) & 15) != 0;
         const size_t want = align4(j.n) + 4;
         if (st) {
           DQ_HIP(hipMemcpyAsync(d_map_align_, j.d_in, (size_t)j.n * 4, hipMemcpyDeviceToDevice, stream));
@@ -2546,11 +2601,12 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
         DQ_HIP(hipGetLastError());
         timed_end(ST_CELLS, 0.0, stream);
         timed_begin(stream);
-        launch_map(dt, 1, j.k, nb, stream);
+        launch_map(dt, 1, j.k, nb, stream, lb);
         DQ_HIP(hipGetLastError());
-        timed_end(ST_MAP, 8.0 * (double)j.n, stream, (double)j.n);
-        if (st)
-          DQ_HIP(hipMemcpyAsync(j.d_out, d_map_align_ + want, (size_t)j.n * 4, hipMemcpyDeviceToDevice, stream));
+        timed_end(ST_MAP, (lb ? 4.0 + lb : 8.0) * (double)j.n, stream, (double)j.n);
+        if (st)   // (exactly the n colours or labels)
+          DQ_HIP(hipMemcpyAsync(const_cast<void*>(dst_of(j)), d_map_align_ + want, (size_t)j.n * (lb ? (size_t)lb : 4),
+                                hipMemcpyDeviceToDevice, stream));
       }
     }
   }
@@ -2567,6 +2623,14 @@ void Engine::map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sy
 void Engine::map(const uint32_t* d_in, uint32_t n, uint32_t* d_out,
                  const uint32_t* ct, int k, hipStream_t stream) {
   MapJob j{d_in, n, d_out, ct, k};
+  map_many(&j, 1, stream);
+}
+
+void Engine::map_labels(const uint32_t* d_in, uint32_t n, void* d_labels, int label_bytes,
+                        const uint32_t* ct, int k, hipStream_t stream) {
+  MapJob j{d_in, n, nullptr, ct, k};
+  j.d_labels = d_labels;
+  j.label_bytes = label_bytes;
   map_many(&j, 1, stream);
 }
 

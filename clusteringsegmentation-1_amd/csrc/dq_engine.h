@@ -83,6 +83,11 @@ struct FrameJob {
   const uint32_t* d_in = nullptr;    // device, n points (this process's rows)
   uint32_t n = 0;
   uint32_t* d_out = nullptr;         // device, mapped colours (nullptr: cluster only)
+  // device, n cluster labels of label_bytes (1 / 2 / 4) each: every pixel's
+  // index into the deduplicated colortable (nullptr: none).  Whole packed
+  // frames of one process (no row shards, no BGR24 frame).
+  void* d_labels = nullptr;
+  int label_bytes = 0;
   int k = 0;                         // requested clusters
   uint32_t* ct = nullptr;            // host, >= k entries
   // row-tile sharding
@@ -114,7 +119,8 @@ struct KernelStat {
   uint64_t launches = 0;
   double ms = 0.0;
   double bytes = 0.0;   // engine-model bytes (4 B per packed point read,
-                        //   3 B per planar point read or written, 8 B per mapped pixel)
+                        //   3 B per planar point read or written, 8 B per mapped pixel,
+                        //   4 + label_bytes per label-mapped pixel)
   double units = 0.0;   // points (pixels) the launches processed
 };
 enum StatKind { ST_INIT = 0, ST_SPLIT, ST_KMEANS, ST_KLAST, ST_EPILOGUE, ST_PARTITION,
@@ -185,6 +191,10 @@ class Engine {
   // map_colors_mps (DivQuantMapColors.cpp:243-539) on device buffers.
   void map(const uint32_t* d_in, uint32_t n, uint32_t* d_out,
            const uint32_t* ct, int k, hipStream_t stream);
+  // The same map's cluster labels: per pixel the lowest i with ct[i] == its
+  // mapped colour, label_bytes (1 / 2 / 4) each.
+  void map_labels(const uint32_t* d_in, uint32_t n, void* d_labels, int label_bytes,
+                  const uint32_t* ct, int k, hipStream_t stream);
   // pixels per map task (map_many splits larger jobs; 4 n < 2^31 for the
   // output's buffer resource, 16-B aligned sub-jobs)
   static constexpr uint32_t kMapTaskMax = 1u << 28;
@@ -195,7 +205,14 @@ class Engine {
     const uint32_t* ct;   // host colortable
     int k;
     bool bgr = false;     // d_in is a BGR24 frame (3 B per pixel)
+    // Label map: n labels of label_bytes (1 / 2 / 4) each instead of colours
+    // (d_out unused) -- the lowest i with ct[i] == the mapped colour (low 24
+    // bits).  Naturally aligned; packed input only; k - 1 must fit the width.
+    void* d_labels = nullptr;
+    int label_bytes = 0;
   };
+  // (jobs of several output formats: the colour jobs, then the label jobs of
+  // each width -- one launch maps one format)
   // sync = false: enqueue only (the caller synchronises and collects the timing)
   void map_many(const MapJob* jobs, int njobs, hipStream_t stream, bool sync = true);
 

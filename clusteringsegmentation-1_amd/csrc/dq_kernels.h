@@ -232,7 +232,18 @@ struct alignas(16) MapTask {
   uint32_t block_begin;     // first map workgroup of this task
   uint32_t grp_per_block;   // groups of kMapPx pixels per workgroup
   int32_t bgr;              // in is a BGR24 frame (3 B per pixel, 8-B aligned; map_lds_kernel only)
+  // 0: out gets the mapped colours.  1 / 2 / 4: out gets n cluster labels of
+  // that many bytes each (16-B aligned) -- the caller's index of the answer
+  // colour, from the task's label table: k u16 (sorted-palette index ->
+  // label) behind the palette at pal + map_label_off(k).  The single-candidate
+  // compact record of such a task carries the label, not the colour
+  // (build_cells_kernel), so a label task and a colour task never share a
+  // cell table.  Packed input only.
+  int32_t labels;
 };
+static_assert(sizeof(MapTask) == 80, "the label width fills MapTask's padding: the colour kernels' task loads are unchanged");
+// words from a task's palette to its label table (the palette padded to 16 B)
+constexpr uint32_t map_label_off(uint32_t k) { return (k + 3u) & ~3u; }
 
 // Map: candidate records per colour cell for every task (one launch), then
 // the per-pixel argmin over (squared distance, MPS visit rank) for every
@@ -240,14 +251,17 @@ struct alignas(16) MapTask {
 // [block_begin, block_begin + ceil(n / kMapPx / grp_per_block))).
 void launch_build_cells(const MapTask* tasks, int ntasks, int kmax, hipStream_t stream);
 uint32_t map_groups_per_block(uint32_t n);
-void launch_map(const MapTask* tasks, int ntasks, int kmax, uint32_t nblocks, hipStream_t stream);
+// (launch_map / launch_map_lds: every task of a launch has the same
+// MapTask::labels -- one launch maps one output format)
+void launch_map(const MapTask* tasks, int ntasks, int kmax, uint32_t nblocks, hipStream_t stream,
+                int labels = 0);
 // K <= 1024: the same map with the compact cell table staged in LDS (one
 // 1024-thread workgroup per CU); map_lds_blocks gives each task's share of
 // the grid (block_begin / grp_per_block set by the caller from it).
 constexpr int kMapLdsBlock = 1024;
 // bgr: every task's input is a BGR24 frame (MapTask::bgr), else every task's is packed.
 void launch_map_lds(const MapTask* tasks, int ntasks, int kmax, uint32_t nblocks, bool bgr,
-                    hipStream_t stream);
+                    hipStream_t stream, int labels = 0);
 
 // Block histograms of a mapped frame (genHistogramsForBlocks' block loop,
 // ClusteringSegmentation.cpp:420-563).  Blocks of dim x dim pixels, dim 1..4 (the app: 4);

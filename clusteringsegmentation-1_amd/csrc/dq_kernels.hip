@@ -2801,12 +2801,15 @@ __global__ __launch_bounds__(BR * BG * BB) void build_cells_kernel(const MapTask
   r.w = slot[5] | (slot[6] << 16);
   reinterpret_cast<uint4*>(tk.cell_rec)[cell] = r;
   // compact record (K <= 1024): bit 31 -- one candidate, its colour in bits
-  // 0-23 (every filter is an exact elimination, so it is every colour's
+  // 0-23, or for a label task (MapTask::labels) its label (every filter is an exact elimination, so it is every colour's
   // answer); bits 31:30 = 01 -- 2 or 3 candidates, 10-bit indices (unused
   // slots repeat the first); 00 -- count << 16 | cell (count 63: whole palette)
   uint32_t c32;
   if (fcount == 1) {
-    c32 = 0x80000000u | spal_c[slot[0]];
+    // (a label task: the answer's label, from the table behind the palette)
+    typedef const __attribute__((address_space(1))) uint16_t g_cu16;
+    c32 = 0x80000000u | (tk.labels ? (uint32_t)((g_cu16*)(tk.pal + map_label_off((uint32_t)k)))[slot[0]]
+                                   : spal_c[slot[0]]);
   } else if (fcount >= 2 && fcount <= 3) {
     const uint32_t j0 = slot[0], j1 = slot[1];
     const uint32_t j2 = fcount > 2 ? slot[2] : j0;
@@ -2839,7 +2842,15 @@ __device__ __forceinline__ uint32_t entry_from_sad(uint32_t S, uint32_t sad) {
   return (x & 3u) == 0 ? (x >> 2) : ((S - sad) >> 2);
 }
 
-template <bool kWide>
+// Label output (LB = 1 / 2 / 4 bytes per label; 0: the mapped colour): the
+// winning entry's label from the task's table (sorted index -> caller's
+// index, MapTask::labels) instead of its colour; 8 labels per lane as one
+// 8-B (u8) or 16-B (u16) store, u32 as the colours.  The colour kernels are
+// the LB = 0 instantiations: every label branch is `if constexpr`.
+template <int LB>
+using label_t = std::conditional_t<LB == 1, uint8_t, std::conditional_t<LB == 2, uint16_t, uint32_t>>;
+
+template <bool kWide, int LB = 0>
 __global__ __launch_bounds__(kBlock) void map_kernel(const MapTask* __restrict__ tasks, int ntasks) {
   int ti = 0;
   while (ti + 1 < ntasks && tasks[ti + 1].block_begin <= blockIdx.x) ++ti;
@@ -2867,6 +2878,18 @@ __global__ __launch_bounds__(kBlock) void map_kernel(const MapTask* __restrict__
   g_cu4* rec4 = (g_cu4*)tk.cell_rec;
   g_cu4* in4 = (g_cu4*)in;
   typedef __attribute__((address_space(1))) u32x4 g_u4;
+  // entry j's output: its colour, or its label (the table stays in global
+  // memory: K = 16384 leaves no LDS for it)
+  g_cu16* glab = (g_cu16*)(tk.pal + map_label_off((uint32_t)k));
+  // (j >= k: the inline pass of a cell with no inline candidates -- a whole-
+  // palette cell -- has only the sentinel's keys; its index is k, or past
+  // any table at k = 16384, where 4 k leaves v_sad_u16's 16-bit halves.  The
+  // colour read of it stays inside LDS's zero-reading range and the slow path
+  // replaces the answer; a global read must not be issued)
+  auto output_of = [&](uint32_t j) -> uint32_t {
+    if constexpr (LB != 0) return j < (uint32_t)k ? (uint32_t)glab[j] : 0u;
+    else return spal[j].x;
+  };
 
   // exact (d, rank) key of palette entry j for pixel p (S = 4 s + 1)
   auto full_key = [&](uint32_t p, uint32_t S, uint32_t j) -> uint64_t {
@@ -2917,7 +2940,7 @@ __global__ __launch_bounds__(kBlock) void map_kernel(const MapTask* __restrict__
         best = key < best ? key : best;
       }
       const uint32_t sad = (uint32_t)(kWide ? (best & 0xFFFFFFFFull) : (best & 0xFFFu));
-      res[e] = spal[entry_from_sad<kWide>(S, sad)].x;
+      res[e] = output_of(entry_from_sad<kWide>(S, sad));
       over[e] = (r[e][0] & 0xFFFF) > (uint32_t)kCellInline;
     }
     bool any_over = false;
@@ -2937,12 +2960,22 @@ __global__ __launch_bounds__(kBlock) void map_kernel(const MapTask* __restrict__
           for (uint32_t m = 0; m < cnt; ++m) { const uint64_t key = full_key(p, S, lst[m]); best = key < best ? key : best; }
         }
         const uint32_t sad = (uint32_t)(kWide ? (best & 0xFFFFFFFFull) : (best & 0xFFFu));
-        res[e] = spal[entry_from_sad<kWide>(S, sad)].x;
+        res[e] = output_of(entry_from_sad<kWide>(S, sad));
       }
     }
     if (have) {
-      ((g_u4*)as_gw(out))[2 * g] = (u32x4){res[0], res[1], res[2], res[3]};
-      ((g_u4*)as_gw(out))[2 * g + 1] = (u32x4){res[4], res[5], res[6], res[7]};
+      if constexpr (LB == 1) {
+        typedef uint32_t u32x2w __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(1))) u32x2w g_u2;
+        ((g_u2*)as_gw(out))[g] = (u32x2w){res[0] | (res[1] << 8) | (res[2] << 16) | (res[3] << 24),
+                                          res[4] | (res[5] << 8) | (res[6] << 16) | (res[7] << 24)};
+      } else if constexpr (LB == 2) {
+        ((g_u4*)as_gw(out))[g] = (u32x4){res[0] | (res[1] << 16), res[2] | (res[3] << 16),
+                                         res[4] | (res[5] << 16), res[6] | (res[7] << 16)};
+      } else {
+        ((g_u4*)as_gw(out))[2 * g] = (u32x4){res[0], res[1], res[2], res[3]};
+        ((g_u4*)as_gw(out))[2 * g + 1] = (u32x4){res[4], res[5], res[6], res[7]};
+      }
     }
   }
   // tail (n % kMapPx points): the task's first workgroup, one point per lane, whole palette
@@ -2953,7 +2986,8 @@ __global__ __launch_bounds__(kBlock) void map_kernel(const MapTask* __restrict__
     uint64_t best = ~0ull;
     for (int j = 0; j < k; ++j) { const uint64_t key = full_key(p, S, (uint32_t)j); best = key < best ? key : best; }
     const uint32_t sad = (uint32_t)(kWide ? (best & 0xFFFFFFFFull) : (best & 0xFFFu));
-    as_gw(out)[t] = spal[entry_from_sad<kWide>(S, sad)].x;
+    typedef __attribute__((address_space(1))) label_t<LB> g_lab;
+    ((g_lab*)as_gw(out))[t] = (label_t<LB>)output_of(entry_from_sad<kWide>(S, sad));
   }
 }
 
@@ -2992,9 +3026,15 @@ __device__ __forceinline__ u32x4 bgr12_to_px4(uint32_t w0, uint32_t w1, uint32_t
   return o;
 }
 
-template <bool BGR>
+// Label output (LB, as map_kernel): the one-candidate record of a label task
+// holds the label itself, the other answers go through the label table in
+// LDS (k u16 behind the start LUT); a lane's two chunks of 4 labels are one
+// 4-B (u8), 8-B (u16) or 16-B (u32) buffer store each, contiguous across the
+// wave.  Packed input only.
+template <bool BGR, int LB = 0>
 __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __restrict__ tasks,
                                                               int ntasks) {
+  static_assert(!(BGR && LB != 0), "label maps read packed pixels");
   int ti = 0;
   while (ti + 1 < ntasks && tasks[ti + 1].block_begin <= blockIdx.x) ++ti;
   const MapTask tk = tasks[ti];
@@ -3005,6 +3045,7 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
   uint32_t* squeue = smem + kCells;                           // per wave: kMapQ pixels / results
   uint2* spal = reinterpret_cast<uint2*>(squeue + (kMapLdsBlock / 64) * kMapQ);   // k+1
   uint16_t* slut = reinterpret_cast<uint16_t*>(reinterpret_cast<uint32_t*>(spal) + 2 * (k + 1));
+  uint16_t* slab = slut + 768;   // k labels (label maps only)
   typedef const __attribute__((address_space(1))) uint16_t g_cu16;
   {
     g_cu4* t4 = (g_cu4*)tk.cell_c32;
@@ -3019,6 +3060,10 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
     }
     g_cu16* glut = (g_cu16*)tk.lut;
     for (int i = threadIdx.x; i < 766; i += kMapLdsBlock) slut[i] = (uint16_t)(4u * glut[i] + 1u);   // S = 4s + 1
+    if constexpr (LB != 0) {
+      g_cu16* glab = (g_cu16*)(tk.pal + map_label_off((uint32_t)k));
+      for (int i = threadIdx.x; i < k; i += kMapLdsBlock) slab[i] = glab[i];
+    }
   }
   __syncthreads();
   const uint32_t lane = lane_id();
@@ -3058,7 +3103,7 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
   // stores at kOOB (dropped), so every iteration issues the same count of
   // vector-memory operations after its loads (see the loop's top)
   const __amdgpu_buffer_rsrc_t orsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)tk.out, (short)0, (int)(4ull * n), 0x00020000);   // (n <= 2^28: Engine::map_many)
+      __builtin_amdgcn_make_buffer_rsrc((void*)tk.out, (short)0, (int)((LB != 0 ? (uint64_t)LB : 4ull) * n), 0x00020000);   // (n <= 2^28: Engine::map_many)
 
   // (c2 - 2 dot) << 12 | sad, as (c2 << 12) - (dot << 13) + sad: the low 12
   // bits of the first two terms are zero and sad < 4096, so the OR is an add
@@ -3073,7 +3118,9 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
     return __builtin_amdgcn_sad_u16(4u * j, S, hi);
   };
   auto answer = [&](uint32_t S, uint32_t best) -> uint32_t {
-    return spal[entry_from_sad<false>(S, best & 0xFFFu)].x;
+    const uint32_t j = entry_from_sad<false>(S, best & 0xFFFu);
+    if constexpr (LB != 0) return slab[j];
+    else return spal[j].x;
   };
   // the record of p's cell (the top byte of p is ignored everywhere): byte
   // offset 4 * cell = (R'' << 10) + (G'' << 5) + B'' with X'' = (X >> 3) << 2,
@@ -3092,12 +3139,18 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
     const uint32_t S = start_of(p);
     if (r & 0x40000000u) {   // 2-3 inline candidates (unused slots repeat the first)
       const uint32_t j0 = r & 0x3FFu, j1 = (r >> 10) & 0x3FFu, j2 = (r >> 20) & 0x3FFu;
-      const uint32_t q0 = spal[j0].x, q1 = spal[j1].x, q2 = spal[j2].x;
-      const uint32_t k0 = key(p, S, j0), k1 = key(p, S, j1), k2 = key(p, S, j2);
       // keys of distinct entries differ (the tie field is |4j - S|, S odd):
       // the answer is the winning candidate's own entry
-      const uint32_t best = min(k0, min(k1, k2));
-      return best == k0 ? q0 : (best == k1 ? q1 : q2);
+      if constexpr (LB != 0) {
+        const uint32_t k0 = key(p, S, j0), k1 = key(p, S, j1), k2 = key(p, S, j2);
+        const uint32_t best = min(k0, min(k1, k2));
+        return slab[best == k0 ? j0 : (best == k1 ? j1 : j2)];
+      } else {
+        const uint32_t q0 = spal[j0].x, q1 = spal[j1].x, q2 = spal[j2].x;
+        const uint32_t k0 = key(p, S, j0), k1 = key(p, S, j1), k2 = key(p, S, j2);
+        const uint32_t best = min(k0, min(k1, k2));
+        return best == k0 ? q0 : (best == k1 ? q1 : q2);
+      }
     }
     const uint32_t cnt = (r >> 16) & 0x3Fu;
     uint32_t best = 0xFFFFFFFFu;
@@ -3159,6 +3212,13 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
       const uint32_t r = inl ? r0 : 0u, p = inl ? px[e] : 0u;
       const uint32_t S = start_of(p);
       const uint32_t j0 = r & 0x3FFu, j1 = (r >> 10) & 0x3FFu, j2 = (r >> 20) & 0x3FFu;
+      if constexpr (LB != 0) {
+        // (the winner's label: one read of the table, entry 0 for the others)
+        const uint32_t k0 = key(p, S, j0), k1 = key(p, S, j1), k2 = key(p, S, j2);
+        const uint32_t best = min(k0, min(k1, k2));
+        const uint32_t li = slab[best == k0 ? j0 : (best == k1 ? j1 : j2)];
+        res[e] = inl ? li : (r0 & 0xFFFFFFu);   // (one candidate: its label)
+      } else {
       const uint32_t q0 = spal[j0].x, q1 = spal[j1].x, q2 = spal[j2].x;
       const uint32_t k0 = key(p, S, j0), k1 = key(p, S, j1), k2 = key(p, S, j2);
       // keys of distinct entries differ (the tie field is |4j - S|, S odd):
@@ -3166,6 +3226,7 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
       const uint32_t best = min(k0, min(k1, k2));
       const uint32_t qi = best == k0 ? q0 : (best == k1 ? q1 : q2);
       res[e] = inl ? qi : (r0 & 0xFFFFFFu);   // (one candidate: its colour)
+      }
     }
     // cells with more candidates: queue (lane order: an exclusive scan of the
     // lanes' counts), resolve cooperatively, read back
@@ -3210,10 +3271,22 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
     {
       // (nontemporal, aux bit 1: streamed past the caches -- the next call's
       // root pass found its frame in L2 / MALL instead of the map's output)
+      if constexpr (LB == 1) {   // a chunk's 4 labels: 4 B per lane, 256 B per wave and store
+        const int oa = (int)(have_a ? 4u * chunk(g, 0) : kOOB);
+        const int ob = (int)(have_b ? 4u * chunk(g, 1) : kOOB);
+        __builtin_amdgcn_raw_buffer_store_b32(res[0] | (res[1] << 8) | (res[2] << 16) | (res[3] << 24), orsrc, oa, 0, 2);
+        __builtin_amdgcn_raw_buffer_store_b32(res[4] | (res[5] << 8) | (res[6] << 16) | (res[7] << 24), orsrc, ob, 0, 2);
+      } else if constexpr (LB == 2) {   // 8 B per lane, 512 B per wave and store
+        const int oa = (int)(have_a ? 8u * chunk(g, 0) : kOOB);
+        const int ob = (int)(have_b ? 8u * chunk(g, 1) : kOOB);
+        __builtin_amdgcn_raw_buffer_store_b64((u32x2v){res[0] | (res[1] << 16), res[2] | (res[3] << 16)}, orsrc, oa, 0, 2);
+        __builtin_amdgcn_raw_buffer_store_b64((u32x2v){res[4] | (res[5] << 16), res[6] | (res[7] << 16)}, orsrc, ob, 0, 2);
+      } else {
       const int oa = (int)(have_a ? 16u * (bgr ? 2u * g : chunk(g, 0)) : kOOB);
       const int ob = (int)(have_b ? 16u * (bgr ? 2u * g + 1u : chunk(g, 1)) : kOOB);
       __builtin_amdgcn_raw_buffer_store_b128((u32x4){res[0], res[1], res[2], res[3]}, orsrc, oa, 0, 2);
       __builtin_amdgcn_raw_buffer_store_b128((u32x4){res[4], res[5], res[6], res[7]}, orsrc, ob, 0, 2);
+      }
     }
   };
   // (the prologue issues what an iteration issues after its loads, so the
@@ -3241,9 +3314,11 @@ __global__ __launch_bounds__(kMapLdsBlock) void map_lds_kernel(const MapTask* __
     const uint32_t S = start_of(p);
     uint32_t best = 0xFFFFFFFFu;
     for (int j = 0; j < k; ++j) best = min(best, key(p, S, (uint32_t)j));
-    as_gw(tk.out)[t] = answer(S, best);
+    typedef __attribute__((address_space(1))) label_t<LB> g_lab;
+    ((g_lab*)as_gw(tk.out))[t] = (label_t<LB>)answer(S, best);
   }
 }
+
 
 // The cursor scan of one record's tiles from their per-(tile, wave) counts
 // (launch_fix_cursors).
@@ -3412,26 +3487,47 @@ uint32_t map_groups_per_block(uint32_t n) {
 }
 
 void launch_map_lds(const MapTask* tasks, int ntasks, int kmax, uint32_t nblocks, bool bgr,
-                    hipStream_t stream) {
+                    hipStream_t stream, int labels) {
   if (ntasks <= 0 || nblocks == 0) return;
+  // (a label map: its table of kmax u16 behind the start LUT, 2 KB at K = 1024)
   const size_t lds = (size_t)kCells * 4 + (size_t)(kMapLdsBlock / 64) * kMapQ * 4 +
-                     (size_t)(kmax + 1) * 8 + 768 * 2;
+                     (size_t)(kmax + 1) * 8 + 768 * 2 + (labels ? (size_t)kmax * 2 : 0);
   static bool attr = false;
   if (!attr) {   // more than 64 KB of dynamic LDS
     (void)hipFuncSetAttribute((const void*)map_lds_kernel<false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)map_lds_kernel<true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)map_lds_kernel<false, 1>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)map_lds_kernel<false, 2>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)map_lds_kernel<false, 4>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  if (bgr) map_lds_kernel<true><<<dim3(nblocks), dim3(kMapLdsBlock), lds, stream>>>(tasks, ntasks);
+  const dim3 g(nblocks), b(kMapLdsBlock);
+  if (labels == 1) map_lds_kernel<false, 1><<<g, b, lds, stream>>>(tasks, ntasks);
+  else if (labels == 2) map_lds_kernel<false, 2><<<g, b, lds, stream>>>(tasks, ntasks);
+  else if (labels == 4) map_lds_kernel<false, 4><<<g, b, lds, stream>>>(tasks, ntasks);
+  else if (bgr) map_lds_kernel<true><<<dim3(nblocks), dim3(kMapLdsBlock), lds, stream>>>(tasks, ntasks);
   else map_lds_kernel<false><<<dim3(nblocks), dim3(kMapLdsBlock), lds, stream>>>(tasks, ntasks);
 }
 
-void launch_map(const MapTask* tasks, int ntasks, int kmax, uint32_t nblocks, hipStream_t stream) {
+template <int LB>
+static void launch_map_labels(const MapTask* tasks, int ntasks, bool wide, uint32_t nblocks, size_t lds,
+                              hipStream_t stream) {
+  if (wide) map_kernel<true, LB><<<dim3(nblocks), dim3(kBlock), lds, stream>>>(tasks, ntasks);
+  else map_kernel<false, LB><<<dim3(nblocks), dim3(kBlock), lds, stream>>>(tasks, ntasks);
+}
+
+void launch_map(const MapTask* tasks, int ntasks, int kmax, uint32_t nblocks, hipStream_t stream, int labels) {
   if (ntasks <= 0 || nblocks == 0) return;
   const size_t lds = (size_t)(kmax + 1) * 8 + 768 * 2;
-  if (kmax <= 1024)   // 12-bit rank field in the 32-bit key
+  if (labels == 1) launch_map_labels<1>(tasks, ntasks, kmax > 1024, nblocks, lds, stream);
+  else if (labels == 2) launch_map_labels<2>(tasks, ntasks, kmax > 1024, nblocks, lds, stream);
+  else if (labels == 4) launch_map_labels<4>(tasks, ntasks, kmax > 1024, nblocks, lds, stream);
+  else if (kmax <= 1024)   // 12-bit rank field in the 32-bit key
     map_kernel<false><<<dim3(nblocks), dim3(kBlock), lds, stream>>>(tasks, ntasks);
   else
     map_kernel<true><<<dim3(nblocks), dim3(kBlock), lds, stream>>>(tasks, ntasks);

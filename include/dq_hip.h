@@ -185,6 +185,35 @@ int dq_hip_cut_bits_dev(int device, const uint32_t *d_in, uint32_t n, uint32_t *
 int dq_hip_map_dev(int device, const uint32_t *d_in, uint32_t n,
                    uint32_t *d_out, const uint32_t *ct, int k, void *stream);
 
+/* ---- cluster labels (what a segmentation consumer works with) ------------
+ * The label of pixel p for a colortable ct[0..k): with c the colour
+ * dq_hip_map_dev writes for p, the lowest i with (ct[i] & 0xFFFFFF) ==
+ * (c & 0xFFFFFF) -- unique for the deduplicated colortables the quant entry
+ * points return (the command line's "tag"), well defined for palettes with
+ * duplicate entries.  Labels are uint8_t, uint16_t or uint32_t: label_bytes =
+ * 1, 2 or 4.  Any other label_bytes, a width that cannot hold index k - 1
+ * (for the quant entries: the requested k) or a label pointer that is not
+ * naturally aligned is a bad argument: -1, nothing runs.  d_labels: n labels
+ * on `device`; exactly those n * label_bytes bytes are written.  Input is
+ * packed 0x00RRGGBB (top byte ignored).
+ * dq_hip_map_labels_dev: the labels of dq_hip_map_dev's colours; stream and
+ * synchronisation as dq_hip_map_dev.  Returns 0 or < 0. */
+int dq_hip_map_labels_dev(int device, const uint32_t *d_in, uint32_t n, void *d_labels,
+                          int label_bytes, const uint32_t *ct, int k, void *stream);
+/* dq_hip_quant_batch_dev (uniq = 1) with labels in place of colours: the same
+ * ct (frame i at ct + i*k), k_out and return value; frame i's labels index
+ * its deduplicated colortable ct + i*k [0..k_out[i]).  uniq = 0: every frame
+ * through the weighted path, as dq_hip_quant_weighted_dev would, one after
+ * the other.  Synchronous on return. */
+int dq_hip_quant_labels_batch_dev(int device, int nframes, const uint32_t *const *d_in,
+                                  const uint32_t *n, void *const *d_labels, int label_bytes,
+                                  uint32_t k, uint32_t *ct, uint32_t *k_out, int uniq,
+                                  int max_iters, void *stream);
+/* Host pointers, the current device: dq_hip_quant with n labels (label_bytes
+ * each) in place of the mapped colours. */
+int dq_hip_quant_labels(const uint32_t *in, uint32_t n, void *labels, int label_bytes,
+                        uint32_t *k, uint32_t *ct, int uniq);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
