@@ -17,6 +17,9 @@ Device-resident entry points (torch tensors / raw device pointers on HBM):
     quant_device, quant_batch_device, cluster_device, map_device
 Cluster labels (each pixel's index into the colortable, u8 / u16 / u32):
     map_labels_device, quant_labels_batch_device, quant_labels
+Connected regions of a label map (equal labels joined by 4- / 8-neighbours,
+numbered in raster order) with area, bounding box, first pixel, colour sums:
+    label_regions_device, label_regions
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -83,6 +86,10 @@ def lib():
         "dq_hip_quant_labels_batch_dev": ([c.c_int, c.c_int, vp, vp, vp, c.c_int, c.c_uint32, vp, vp, c.c_int,
                                            c.c_int, vp], c.c_int),
         "dq_hip_quant_labels": ([vp, c.c_uint32, vp, c.c_int, u32p, vp, c.c_int], c.c_int),
+        "dq_hip_label_regions_dev": ([c.c_int, vp, c.c_int, c.c_uint32, c.c_uint32, c.c_int, vp, c.c_uint32, vp, vp,
+                                      vp, vp, vp, vp, vp], c.c_int64),
+        "dq_hip_label_regions": ([vp, c.c_int, c.c_uint32, c.c_uint32, c.c_int, vp, c.c_uint32, vp, vp, vp, vp, vp,
+                                  vp], c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -560,6 +567,108 @@ def quant_labels(pixels, num_clusters, all_pixels_unique=1, dtype=None):
                                  int(all_pixels_unique)) < 0:
         raise DivQuantError("dq_hip_quant_labels: bad arguments")
     return labels, ct[:k.value].copy()
+
+
+# ---------------------------------------------------------------------------
+# Connected regions of a label map (include/dq_hip.h, "connected regions"):
+# pixels joined by a path of 4- / 8-neighbours with equal labels, numbered in
+# raster order of their first pixel.  Exact integers, independent of scheduling.
+REGION_TILE = 64          # DQ_HIP_REGION_TILE: the tile pass works on 64 x 64 tiles
+REGION_MAX_SIDE = 65535   # width, height (the Coord layout)
+REGION_MAX_PIXELS = (1 << 31) - 1
+
+
+def _region_shape(width, height, connectivity):
+    width, height = int(width), int(height)
+    if not (1 <= width <= REGION_MAX_SIDE and 1 <= height <= REGION_MAX_SIDE) or width * height > REGION_MAX_PIXELS:
+        raise ValueError("a %d x %d map: sides are 1..65535, at most 2^31 - 1 pixels" % (width, height))
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity is 4 or 8, not %r" % (connectivity,))
+    return width, height
+
+
+def _words(t, n, what):
+    """A contiguous tensor / array of at least n 4-byte elements."""
+    if _label_width(t, n, what) != 4:
+        raise ValueError("%s: 4-byte elements (int32 / uint32 storage)" % what)
+
+
+def label_regions_device(t_labels, width, height, t_regions, connectivity=8, stats_capacity=0, t_pixels=None,
+                         device=0, stream=None):
+    """Connected regions of a device-resident width x height label map.
+    t_labels: contiguous, 1, 2 or 4 bytes per label; t_regions: contiguous,
+    4-byte elements, gets each pixel's region id.  Returns (R, stats): R the
+    region count, stats a dict of device tensors holding the first
+    min(R, stats_capacity) regions -- "area", "bbox" (x0, y0, x1, y1,
+    inclusive), "first" (y * width + x of the first pixel), "label" (int32
+    storage of the uint32 values) and, with t_pixels (the packed 0x00RRGGBB
+    frame), "sums" (int64: R, G, B sums) -- empty at capacity 0.  Synchronous.
+    ValueError for bad tensors or shapes (nothing runs)."""
+    width, height = _region_shape(width, height, connectivity)
+    n = width * height
+    lb = _label_width(t_labels, n)
+    _words(t_regions, n, "t_regions")
+    if t_pixels is not None:
+        _words(t_pixels, n, "t_pixels")
+    cap = int(stats_capacity)
+    if not 0 <= cap <= 0xFFFFFFFF:
+        raise ValueError("stats_capacity %d" % cap)
+    st = {}
+    if cap:
+        import torch
+        dev = f"cuda:{device}"
+        st = {"area": torch.empty(cap, dtype=torch.int32, device=dev),
+              "bbox": torch.empty((cap, 4), dtype=torch.int32, device=dev),
+              "first": torch.empty(cap, dtype=torch.int32, device=dev),
+              "label": torch.empty(cap, dtype=torch.int32, device=dev)}
+        if t_pixels is not None:
+            st["sums"] = torch.empty((cap, 3), dtype=torch.int64, device=dev)
+    opt = lambda name: _dptr(st[name]) if name in st else None  # noqa: E731
+    r = lib().dq_hip_label_regions_dev(device, _dptr(t_labels), lb, width, height, connectivity, _dptr(t_regions),
+                                       cap, opt("area"), opt("bbox"), opt("first"), opt("label"),
+                                       _dptr(t_pixels) if t_pixels is not None else None, opt("sums"),
+                                       _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_label_regions_dev: bad arguments")
+    return int(r), {k: v[:min(int(r), cap)] for k, v in st.items()}
+
+
+def label_regions(labels2d, connectivity=8, pixels=None):
+    """Connected regions of a host (H, W) label map of 1-, 2- or 4-byte
+    integers.  Returns (regions2d, stats): regions2d (H, W) uint32 and stats a
+    dict of numpy arrays sized to the region count R -- "area" (R,), "bbox"
+    (R, 4: x0, y0, x1, y1 inclusive), "first" (R,), "label" (R,), all uint32,
+    and with pixels (H * W packed 0x00RRGGBB words) "sums" (R, 3) uint64.
+    Two calls: one for the map and R, one with room for R regions."""
+    lab = np.asarray(labels2d)
+    if lab.ndim != 2 or lab.size == 0:
+        raise ValueError("labels2d must be a non-empty (H, W) array")
+    if lab.dtype.kind not in "ui" or lab.dtype.itemsize not in (1, 2, 4):
+        raise ValueError("labels are 1-, 2- or 4-byte integers, not %s" % lab.dtype)
+    lab = np.ascontiguousarray(lab)
+    h, w = lab.shape
+    _region_shape(w, h, connectivity)
+    px = None
+    if pixels is not None:
+        px = _u32(pixels).reshape(-1)
+        if px.size != lab.size:
+            raise ValueError("%d pixels for %d labels" % (px.size, lab.size))
+    _require_gpu()
+    regions = np.zeros((h, w), np.uint32)
+    call = lib().dq_hip_label_regions
+    r = call(_ptr(lab), lab.dtype.itemsize, w, h, connectivity, _ptr(regions), 0, None, None, None, None, None, None)
+    if r < 0:
+        raise DivQuantError("dq_hip_label_regions: bad arguments")
+    st = {"area": np.zeros(r, np.uint32), "bbox": np.zeros((r, 4), np.uint32), "first": np.zeros(r, np.uint32),
+          "label": np.zeros(r, np.uint32)}
+    if px is not None:
+        st["sums"] = np.zeros((r, 3), np.uint64)
+    r2 = call(_ptr(lab), lab.dtype.itemsize, w, h, connectivity, _ptr(regions), r, _ptr(st["area"]), _ptr(st["bbox"]),
+              _ptr(st["first"]), _ptr(st["label"]), _ptr(px) if px is not None else None,
+              _ptr(st["sums"]) if px is not None else None)
+    if r2 != r:
+        raise DivQuantError("dq_hip_label_regions: %d regions, then %d" % (r, r2))
+    return regions, st
 
 
 # ---------------------------------------------------------------------------

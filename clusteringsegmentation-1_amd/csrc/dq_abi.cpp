@@ -23,6 +23,7 @@
 #include "../../include/dq_hip.h"
 #include "../../include/quant_util.h"
 #include "dq_engine.h"
+#include "dq_regions.h"
 #include "dq_weighted.h"
 
 #include <rccl/rccl.h>
@@ -863,6 +864,102 @@ int dq_hip_quant_labels(const uint32_t* in, uint32_t n, void* labels, int label_
   DQ_HIP(hipStreamSynchronize(st));
   *k = (uint32_t)j.k_out;
   return j.num_empty;
+}
+
+// Connected regions of a label map (dq_regions.hip).  Every argument check
+// comes before the first HIP call.
+static bool regions_args_ok(const void* labels, int label_bytes, uint32_t width, uint32_t height,
+                            int connectivity, const uint32_t* regions, uint32_t stats_cap,
+                            const uint32_t* area, const uint32_t* bbox, const uint32_t* first,
+                            const uint32_t* label, const uint32_t* pixels, const uint64_t* sums) {
+  if (label_bytes != 1 && label_bytes != 2 && label_bytes != 4) return false;
+  if (connectivity != 4 && connectivity != 8) return false;
+  if (width == 0 || height == 0 || width > 65535u || height > 65535u ||
+      (uint64_t)width * height > 0x7FFFFFFFull)
+    return false;
+  if (!labels || !regions) return false;
+  if (((uintptr_t)labels & (uintptr_t)(label_bytes - 1)) != 0) return false;
+  for (const void* p : {(const void*)regions, (const void*)area, (const void*)bbox, (const void*)first,
+                        (const void*)label, (const void*)pixels})
+    if (((uintptr_t)p & 3u) != 0) return false;
+  if (((uintptr_t)sums & 7u) != 0) return false;
+  if (sums && !pixels) return false;
+  if (stats_cap > 0 && !area && !bbox && !first && !label && !sums) return false;
+  return true;
+}
+
+// Enqueues the passes on st with scratch owned by the call, waits, returns R.
+static int64_t label_regions_on(hipStream_t st, const void* d_labels, int label_bytes, uint32_t width,
+                                uint32_t height, int connectivity, uint32_t* d_regions, uint32_t stats_cap,
+                                uint32_t* d_area, uint32_t* d_bbox, uint32_t* d_first, uint32_t* d_label,
+                                const uint32_t* d_pixels, uint64_t* d_sums) {
+  uint32_t* scratch = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&scratch, dq::region_scratch_words(width, height) * 4, st));
+  dq::RegionArgs a{d_labels, label_bytes, width,   height,   connectivity, d_regions, stats_cap,
+                   d_area,   d_bbox,      d_first, d_label, d_pixels,     (unsigned long long*)d_sums, scratch};
+  dq::launch_label_regions(a, st);
+  DQ_HIP(hipGetLastError());
+  uint32_t count = 0;
+  DQ_HIP(hipMemcpyAsync(&count, dq::region_count_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipFreeAsync(scratch, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return (int64_t)count;
+}
+
+int64_t dq_hip_label_regions_dev(int device, const void* d_labels, int label_bytes, uint32_t width,
+                                 uint32_t height, int connectivity, uint32_t* d_regions, uint32_t stats_cap,
+                                 uint32_t* d_area, uint32_t* d_bbox, uint32_t* d_first, uint32_t* d_label,
+                                 const uint32_t* d_pixels, uint64_t* d_sums, void* stream) {
+  if (!regions_args_ok(d_labels, label_bytes, width, height, connectivity, d_regions, stats_cap, d_area,
+                       d_bbox, d_first, d_label, d_pixels, d_sums))
+    return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  return label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions, stats_cap, d_area,
+                          d_bbox, d_first, d_label, d_pixels, d_sums);
+}
+
+int64_t dq_hip_label_regions(const void* labels, int label_bytes, uint32_t width, uint32_t height,
+                             int connectivity, uint32_t* regions, uint32_t stats_cap, uint32_t* area,
+                             uint32_t* bbox, uint32_t* first, uint32_t* label, const uint32_t* pixels,
+                             uint64_t* sums) {
+  if (!regions_args_ok(labels, label_bytes, width, height, connectivity, regions, stats_cap, area, bbox, first,
+                       label, pixels, sums))
+    return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height, cap = stats_cap;
+  void* d_labels = nullptr;
+  uint32_t *d_regions = nullptr, *d_area = nullptr, *d_bbox = nullptr, *d_first = nullptr, *d_label = nullptr,
+           *d_pixels = nullptr;
+  uint64_t* d_sums = nullptr;
+  DQ_HIP(hipMallocAsync(&d_labels, n * (size_t)label_bytes, st));
+  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
+  if (cap && area) DQ_HIP(hipMallocAsync((void**)&d_area, cap * 4, st));
+  if (cap && bbox) DQ_HIP(hipMallocAsync((void**)&d_bbox, cap * 16, st));
+  if (cap && first) DQ_HIP(hipMallocAsync((void**)&d_first, cap * 4, st));
+  if (cap && label) DQ_HIP(hipMallocAsync((void**)&d_label, cap * 4, st));
+  if (cap && sums) DQ_HIP(hipMallocAsync((void**)&d_sums, cap * 24, st));
+  if (cap && sums) {
+    DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
+    DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
+  }
+  DQ_HIP(hipMemcpyAsync(d_labels, labels, n * (size_t)label_bytes, hipMemcpyHostToDevice, st));
+  const int64_t count = label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions,
+                                         stats_cap, d_area, d_bbox, d_first, d_label, d_pixels, d_sums);
+  // nothing behind entry min(R, stats_cap) is written
+  const size_t m = std::min((size_t)count, cap);
+  DQ_HIP(hipMemcpyAsync(regions, d_regions, n * 4, hipMemcpyDeviceToHost, st));
+  if (d_area && m) DQ_HIP(hipMemcpyAsync(area, d_area, m * 4, hipMemcpyDeviceToHost, st));
+  if (d_bbox && m) DQ_HIP(hipMemcpyAsync(bbox, d_bbox, m * 16, hipMemcpyDeviceToHost, st));
+  if (d_first && m) DQ_HIP(hipMemcpyAsync(first, d_first, m * 4, hipMemcpyDeviceToHost, st));
+  if (d_label && m) DQ_HIP(hipMemcpyAsync(label, d_label, m * 4, hipMemcpyDeviceToHost, st));
+  if (d_sums && m) DQ_HIP(hipMemcpyAsync(sums, d_sums, m * 24, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  for (void* p : {d_labels, (void*)d_regions, (void*)d_area, (void*)d_bbox, (void*)d_first, (void*)d_label,
+                  (void*)d_pixels, (void*)d_sums})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return count;
 }
 
 // Synthetic frames of the benchmark configs (SURVEY 8c/8d generator) and the

@@ -214,6 +214,55 @@ int dq_hip_quant_labels_batch_dev(int device, int nframes, const uint32_t *const
 int dq_hip_quant_labels(const uint32_t *in, uint32_t n, void *labels, int label_bytes,
                         uint32_t *k, uint32_t *ct, int uniq);
 
+/* ---- connected regions of a label map (labels -> segments on the device) --
+ * A cluster label is not yet a segment: two patches on opposite sides of a
+ * frame share a label.  The reference works on connected regions (floodFill /
+ * floodFillMask with 8-connectivity over tag images, region masks with pixel
+ * counts and bounding rectangles); these entries give them without a host
+ * flood fill.
+ * Definition.  Input: a width x height row-major map of labels, label_bytes
+ * (1, 2 or 4) each, and a connectivity (4 or 8).  Two pixels are in the same
+ * region when a path of 4- / 8-neighbours with EQUAL label values joins them
+ * (u32 labels: all 32 bits are compared -- mask mapped colours first).
+ * Regions are numbered 0 .. R-1 in raster order of their first pixel, the
+ * lowest y * width + x of the region.  The answer is therefore unique: exact
+ * integers that do not depend on scheduling.
+ * d_regions (required): width * height uint32 region ids, always complete.
+ * Stats (each pointer may be NULL), stats_cap entries each; regions with id >=
+ * stats_cap are left out of the stats (the map still numbers them, the return
+ * value still counts them) and nothing behind entry min(R, stats_cap) is
+ * written:
+ *   d_area   pixels of the region
+ *   d_bbox   4 words per region: x0, y0, x1, y1, inclusive
+ *   d_first  y * width + x of the region's first pixel in raster order
+ *   d_label  the region's label value
+ *   d_sums   3 uint64 per region: the R, G and B sums of d_pixels (the packed
+ *            0x00RRGGBB frame the labels came from) over the region; needs
+ *            d_pixels
+ * Both forms return R >= 1 and are synchronous on return.  -1, before any
+ * device work, for: label_bytes not 1/2/4, connectivity not 4/8, width or
+ * height 0 or above 65535 (the Coord layout, x | y << 16) or width * height
+ * above 2^31 - 1, NULL labels or regions, labels / regions / stats arrays not
+ * naturally aligned, d_sums without d_pixels, stats_cap > 0 with every stats
+ * pointer NULL.
+ * Scratch: 4 B per pixel + 4 B per 1024 pixels, allocated and freed in stream
+ * order by the call (calls on two streams may overlap).  The tile pass works
+ * on DQ_HIP_REGION_TILE x DQ_HIP_REGION_TILE pixel tiles. */
+#define DQ_HIP_REGION_TILE 64
+int64_t dq_hip_label_regions_dev(int device, const void *d_labels, int label_bytes,
+                                 uint32_t width, uint32_t height, int connectivity,
+                                 uint32_t *d_regions,
+                                 uint32_t stats_cap, uint32_t *d_area, uint32_t *d_bbox,
+                                 uint32_t *d_first, uint32_t *d_label,
+                                 const uint32_t *d_pixels, uint64_t *d_sums,
+                                 void *stream);
+/* Host pointers, the current device. */
+int64_t dq_hip_label_regions(const void *labels, int label_bytes, uint32_t width,
+                             uint32_t height, int connectivity, uint32_t *regions,
+                             uint32_t stats_cap, uint32_t *area, uint32_t *bbox,
+                             uint32_t *first, uint32_t *label,
+                             const uint32_t *pixels, uint64_t *sums);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
