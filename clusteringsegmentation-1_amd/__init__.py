@@ -20,6 +20,9 @@ Cluster labels (each pixel's index into the colortable, u8 / u16 / u32):
 Connected regions of a label map (equal labels joined by 4- / 8-neighbours,
 numbered in raster order) with area, bounding box, first pixel, colour sums:
     label_regions_device, label_regions
+Adjacency graph of a region map (the pairs of ids that touch, numbered in
+raster order of their first contact) with border, first contact, colour step:
+    region_adjacency_device, region_adjacency
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -90,6 +93,10 @@ def lib():
                                       vp, vp, vp, vp, vp], c.c_int64),
         "dq_hip_label_regions": ([vp, c.c_int, c.c_uint32, c.c_uint32, c.c_int, vp, c.c_uint32, vp, vp, vp, vp, vp,
                                   vp], c.c_int64),
+        "dq_hip_region_adjacency_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, vp, vp, vp, vp, vp,
+                                         c.c_uint32, vp, vp], c.c_int64),
+        "dq_hip_region_adjacency": ([vp, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, vp, vp, vp, vp, vp, c.c_uint32,
+                                     vp], c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -669,6 +676,114 @@ def label_regions(labels2d, connectivity=8, pixels=None):
     if r2 != r:
         raise DivQuantError("dq_hip_label_regions: %d regions, then %d" % (r, r2))
     return regions, st
+
+
+# ---------------------------------------------------------------------------
+# Region adjacency graph of a region map (include/dq_hip.h, "region adjacency
+# graph"): the pairs of ids that touch, numbered in raster order of their first
+# contact, with border length, first contact, colour step sum and the degree of
+# every id.  Exact integers, independent of scheduling.
+ADJACENCY_MAX_PIXELS = 1 << 30   # DQ_HIP_ADJACENCY_MAX_PIXELS: a contact is the word 4 * p + dir
+
+
+def _adjacency_shape(width, height, connectivity):
+    width, height = int(width), int(height)
+    if (not (1 <= width <= REGION_MAX_SIDE and 1 <= height <= REGION_MAX_SIDE)
+            or width * height > ADJACENCY_MAX_PIXELS):
+        raise ValueError("a %d x %d map: sides are 1..65535, at most 2^30 pixels" % (width, height))
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity is 4 or 8, not %r" % (connectivity,))
+    return width, height
+
+
+def region_adjacency_device(t_regions, width, height, connectivity=8, edge_capacity=0, t_pixels=None,
+                            num_regions=0, device=0, stream=None):
+    """The adjacency graph of a device-resident width x height map of region
+    ids (contiguous, 4-byte elements; any id map).  Returns (E, graph): E the
+    edge count, graph a dict of device tensors holding the first
+    min(E, edge_capacity) edges -- "edges" (., 2: a < b), "border" (contacts of
+    the edge), "contact" (., 2: p < q of its first contact; int32 storage of
+    the uint32 values) and, with t_pixels (the packed 0x00RRGGBB frame), "step"
+    (int64: sum of |dR| + |dG| + |dB| over the contacts) -- none of them at
+    capacity 0, and with num_regions > 0 "degree" (num_regions,): the edges at
+    every id, over all E edges (ids in the map must be < num_regions).
+    Synchronous.  ValueError for bad tensors or shapes (nothing runs)."""
+    width, height = _adjacency_shape(width, height, connectivity)
+    n = width * height
+    _words(t_regions, n, "t_regions")
+    if t_pixels is not None:
+        _words(t_pixels, n, "t_pixels")
+    cap, nreg = int(edge_capacity), int(num_regions)
+    if not 0 <= cap <= 0xFFFFFFFF:
+        raise ValueError("edge_capacity %d" % cap)
+    if not 0 <= nreg <= 0xFFFFFFFF:
+        raise ValueError("num_regions %d" % nreg)
+    g = {}
+    if cap or nreg:
+        import torch
+        dev = f"cuda:{device}"
+        if cap:
+            g = {"edges": torch.empty((cap, 2), dtype=torch.int32, device=dev),
+                 "border": torch.empty(cap, dtype=torch.int32, device=dev),
+                 "contact": torch.empty((cap, 2), dtype=torch.int32, device=dev)}
+            if t_pixels is not None:
+                g["step"] = torch.empty(cap, dtype=torch.int64, device=dev)
+        if nreg:
+            g["degree"] = torch.empty(nreg, dtype=torch.int32, device=dev)
+    opt = lambda name: _dptr(g[name]) if name in g else None  # noqa: E731
+    e = lib().dq_hip_region_adjacency_dev(device, _dptr(t_regions), width, height, connectivity, cap, opt("edges"),
+                                          opt("border"), opt("contact"),
+                                          _dptr(t_pixels) if t_pixels is not None else None, opt("step"), nreg,
+                                          opt("degree"), _stream_ptr(stream))
+    if e < 0:
+        raise DivQuantError("dq_hip_region_adjacency_dev: bad arguments")
+    return int(e), {k: (v if k == "degree" else v[:min(int(e), cap)]) for k, v in g.items()}
+
+
+def region_adjacency(regions2d, connectivity=8, pixels=None, num_regions=None):
+    """The adjacency graph of a host (H, W) map of region ids (integers of at
+    most 4 bytes).  Returns a dict of numpy arrays sized to the edge count E --
+    "edges" (E, 2: a < b), "border" (E,), "contact" (E, 2: p < q), all uint32,
+    with pixels (H * W packed 0x00RRGGBB words) "step" (E,) uint64 -- and
+    "degree" (num_regions,) uint32; num_regions=None takes regions2d.max() + 1.
+    Two calls: one for E, one with room for E edges."""
+    reg = np.asarray(regions2d)
+    if reg.ndim != 2 or reg.size == 0:
+        raise ValueError("regions2d must be a non-empty (H, W) array")
+    if reg.dtype.kind not in "ui" or reg.dtype.itemsize > 4:
+        raise ValueError("region ids are integers of at most 4 bytes, not %s" % reg.dtype)
+    if reg.dtype.kind == "i" and reg.min() < 0:
+        raise ValueError("region ids are not negative")
+    reg = _u32(reg)
+    h, w = reg.shape
+    _adjacency_shape(w, h, connectivity)
+    px = None
+    if pixels is not None:
+        px = _u32(pixels).reshape(-1)
+        if px.size != reg.size:
+            raise ValueError("%d pixels for %d region ids" % (px.size, reg.size))
+    nreg = int(reg.max()) + 1 if num_regions is None else int(num_regions)
+    if not int(reg.max()) < nreg <= 0xFFFFFFFF:
+        raise ValueError("num_regions %d for ids up to %d" % (nreg, int(reg.max())))
+    _require_gpu()
+    degree = np.zeros(nreg, np.uint32)
+    call = lib().dq_hip_region_adjacency
+    e = call(_ptr(reg), w, h, connectivity, 0, None, None, None, None, None, 0, None)
+    if e < 0:
+        raise DivQuantError("dq_hip_region_adjacency: bad arguments")
+    g = {"edges": np.zeros((e, 2), np.uint32), "border": np.zeros(e, np.uint32),
+         "contact": np.zeros((e, 2), np.uint32)}
+    if px is not None:
+        g["step"] = np.zeros(e, np.uint64)
+    some = e > 0   # (capacity 0 takes no edge pointers)
+    e2 = call(_ptr(reg), w, h, connectivity, e, _ptr(g["edges"]) if some else None,
+              _ptr(g["border"]) if some else None, _ptr(g["contact"]) if some else None,
+              _ptr(px) if px is not None else None, _ptr(g["step"]) if px is not None and some else None,
+              nreg, _ptr(degree))
+    if e2 != e:
+        raise DivQuantError("dq_hip_region_adjacency: %d edges, then %d" % (e, e2))
+    g["degree"] = degree
+    return g
 
 
 # ---------------------------------------------------------------------------

@@ -23,6 +23,7 @@
 #include "../../include/dq_hip.h"
 #include "../../include/quant_util.h"
 #include "dq_engine.h"
+#include "dq_adjacency.h"
 #include "dq_regions.h"
 #include "dq_weighted.h"
 
@@ -958,6 +959,110 @@ int64_t dq_hip_label_regions(const void* labels, int label_bytes, uint32_t width
   DQ_HIP(hipStreamSynchronize(st));
   for (void* p : {d_labels, (void*)d_regions, (void*)d_area, (void*)d_bbox, (void*)d_first, (void*)d_label,
                   (void*)d_pixels, (void*)d_sums})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return count;
+}
+
+// Region adjacency graph of a region map (dq_adjacency.hip).  Every argument
+// check comes before the first HIP call.
+static bool adjacency_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, int connectivity,
+                              uint32_t edge_cap, const uint32_t* edges, const uint32_t* border,
+                              const uint32_t* contact, const uint32_t* pixels, const uint64_t* step,
+                              uint32_t nregions, const uint32_t* degree) {
+  if (connectivity != 4 && connectivity != 8) return false;
+  // n <= 2^30: a contact is the one word 4 * p + dir, and E < 4 n fits uint32
+  if (width == 0 || height == 0 || width > 65535u || height > 65535u ||
+      (uint64_t)width * height > DQ_HIP_ADJACENCY_MAX_PIXELS)
+    return false;
+  if (!regions) return false;
+  for (const void* p : {(const void*)regions, (const void*)edges, (const void*)border, (const void*)contact,
+                        (const void*)pixels, (const void*)degree})
+    if (((uintptr_t)p & 3u) != 0) return false;
+  if (((uintptr_t)step & 7u) != 0) return false;
+  if (step && !pixels) return false;
+  if (edge_cap > 0 && !edges && !border && !contact && !step) return false;
+  if (degree && nregions == 0) return false;
+  return true;
+}
+
+// Enqueues both halves on st with scratch owned by the call, waits, returns E.
+// One small read-back sits between the halves: the table is sized from the
+// heads the first half counted.
+static int64_t region_adjacency_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                   int connectivity, uint32_t edge_cap, uint32_t* d_edges, uint32_t* d_border,
+                                   uint32_t* d_contact, const uint32_t* d_pixels, uint64_t* d_step,
+                                   uint32_t nregions, uint32_t* d_degree) {
+  uint32_t* counts = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&counts, dq::adjacency_count_words(width, height) * 4, st));
+  dq::AdjacencyArgs a{d_regions, width,    height,   connectivity,
+                      edge_cap,  d_edges,  d_border, d_contact,
+                      d_pixels,  (unsigned long long*)d_step, d_degree, counts, nullptr};
+  if (d_degree) DQ_HIP(hipMemsetAsync(d_degree, 0, (size_t)nregions * 4, st));
+  dq::launch_adjacency_count(a, st);
+  DQ_HIP(hipGetLastError());
+  uint32_t heads = 0, count = 0;
+  DQ_HIP(hipMemcpyAsync(&heads, dq::adjacency_heads_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  if (heads != 0) {   // (no head: no contact, no edge)
+    DQ_HIP(hipMallocAsync(&a.table, dq::adjacency_scratch_bytes(heads, d_step != nullptr), st));
+    dq::launch_adjacency_build(a, heads, st);
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(hipMemcpyAsync(&count, dq::adjacency_edges_word(a), 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipFreeAsync(a.table, st));
+  }
+  DQ_HIP(hipFreeAsync(counts, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return (int64_t)count;
+}
+
+int64_t dq_hip_region_adjacency_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                    int connectivity, uint32_t edge_cap, uint32_t* d_edges, uint32_t* d_border,
+                                    uint32_t* d_contact, const uint32_t* d_pixels, uint64_t* d_step,
+                                    uint32_t nregions, uint32_t* d_degree, void* stream) {
+  if (!adjacency_args_ok(d_regions, width, height, connectivity, edge_cap, d_edges, d_border, d_contact, d_pixels,
+                         d_step, nregions, d_degree))
+    return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  return region_adjacency_on(st, d_regions, width, height, connectivity, edge_cap, d_edges, d_border, d_contact,
+                             d_pixels, d_step, nregions, d_degree);
+}
+
+int64_t dq_hip_region_adjacency(const uint32_t* regions, uint32_t width, uint32_t height, int connectivity,
+                                uint32_t edge_cap, uint32_t* edges, uint32_t* border, uint32_t* contact,
+                                const uint32_t* pixels, uint64_t* step, uint32_t nregions, uint32_t* degree) {
+  if (!adjacency_args_ok(regions, width, height, connectivity, edge_cap, edges, border, contact, pixels, step,
+                         nregions, degree))
+    return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height, cap = edge_cap;
+  uint32_t *d_regions = nullptr, *d_edges = nullptr, *d_border = nullptr, *d_contact = nullptr, *d_pixels = nullptr,
+           *d_degree = nullptr;
+  uint64_t* d_step = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
+  if (cap && edges) DQ_HIP(hipMallocAsync((void**)&d_edges, cap * 8, st));
+  if (cap && border) DQ_HIP(hipMallocAsync((void**)&d_border, cap * 4, st));
+  if (cap && contact) DQ_HIP(hipMallocAsync((void**)&d_contact, cap * 8, st));
+  if (cap && step) {
+    DQ_HIP(hipMallocAsync((void**)&d_step, cap * 8, st));
+    DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
+    DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
+  }
+  if (degree) DQ_HIP(hipMallocAsync((void**)&d_degree, (size_t)nregions * 4, st));
+  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
+  const int64_t count = region_adjacency_on(st, d_regions, width, height, connectivity, edge_cap, d_edges, d_border,
+                                            d_contact, d_pixels, d_step, nregions, d_degree);
+  // nothing behind entry min(E, edge_cap) is written
+  const size_t m = std::min((size_t)count, cap);
+  if (d_edges && m) DQ_HIP(hipMemcpyAsync(edges, d_edges, m * 8, hipMemcpyDeviceToHost, st));
+  if (d_border && m) DQ_HIP(hipMemcpyAsync(border, d_border, m * 4, hipMemcpyDeviceToHost, st));
+  if (d_contact && m) DQ_HIP(hipMemcpyAsync(contact, d_contact, m * 8, hipMemcpyDeviceToHost, st));
+  if (d_step && m) DQ_HIP(hipMemcpyAsync(step, d_step, m * 8, hipMemcpyDeviceToHost, st));
+  if (d_degree) DQ_HIP(hipMemcpyAsync(degree, d_degree, (size_t)nregions * 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  for (void* p : {(void*)d_regions, (void*)d_edges, (void*)d_border, (void*)d_contact, (void*)d_pixels,
+                  (void*)d_step, (void*)d_degree})
     if (p) DQ_HIP(hipFreeAsync(p, st));
   return count;
 }

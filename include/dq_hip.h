@@ -263,6 +263,74 @@ int64_t dq_hip_label_regions(const void *labels, int label_bytes, uint32_t width
                              uint32_t *first, uint32_t *label,
                              const uint32_t *pixels, uint64_t *sums);
 
+/* ---- region adjacency graph of a region map (regions -> the regions that
+ * touch, on the device) --------------------------------------------------
+ * The first thing the reference builds from a tag image is the set of
+ * neighbour tags of every superpixel (SuperpixelImage::parseSuperpixelEdges,
+ * the SuperpixelEdgeTable: the 8 neighbours of every pixel); its merge code
+ * walks those sets.  These entries give the same graph as an edge list with
+ * per-edge stats, without a host scan of the map.
+ * Definition.  Input: a width x height row-major map of uint32 region ids and
+ * a connectivity (4 or 8).  The map is ANY id map (the region map of
+ * dq_hip_label_regions_dev is the intended one): ids need not be connected,
+ * numbered in raster order, or dense.
+ * A contact is a pair of pixel indexes p < q (y * width + x) that are 4- / 8-
+ * neighbours with regions[p] != regions[q].  For one p the possible q are, in
+ * increasing order: right p + 1, down-left p + width - 1 (8 only), down
+ * p + width, down-right p + width + 1 (8 only); nothing wraps around a row end.
+ * An edge is an unordered pair of ids {a, b}, stored a < b, with at least one
+ * contact.  Edges are numbered 0 .. E-1 in the order of their first contacts
+ * (the lexicographically lowest (p, q) of each): the order in which a raster
+ * scan over p, and over q for each p, first meets them.  The answer is
+ * therefore unique: exact integers that do not depend on scheduling.
+ * Edge arrays (each pointer may be NULL), edge_cap entries each; edges with
+ * index >= edge_cap are left out (the return value still counts them) and
+ * nothing behind entry min(E, edge_cap) is written:
+ *   d_edges    2 words per edge: a, b (a < b)
+ *   d_border   the edge's number of contacts
+ *   d_contact  2 words per edge: p, q of its first contact
+ *   d_step     uint64: the sum over the edge's contacts of |dR| + |dG| + |dB|
+ *              between the two pixels of d_pixels (the packed 0x00RRGGBB
+ *              frame, top byte ignored); needs d_pixels.  step / border is the
+ *              mean colour step across the border.
+ * edge_cap == 0 with every edge pointer NULL is the count-only call.
+ * d_degree (may be NULL): nregions words, degree[r] = the number of edges
+ * with r as an end (the size of the reference's neighbour set of tag r), 0
+ * for ids that touch nothing; it counts all E edges whatever edge_cap is.
+ * Every id in the map must then be < nregions (not checked, like Coords).
+ * nregions is ignored without d_degree.
+ * Both forms return E >= 0 and are synchronous on return.  -1, before any
+ * device work, for: NULL regions, connectivity not 4/8, width or height 0 or
+ * above 65535, width * height above DQ_HIP_ADJACENCY_MAX_PIXELS = 2^30, an
+ * array not naturally aligned (4 B; 8 B for d_step), d_step without d_pixels,
+ * edge_cap > 0 with every edge pointer NULL, d_degree with nregions == 0.
+ * Why 2^30: with n <= 2^30 pixels a contact is the single word 4 * p + dir
+ * (dir 0..3 in the order above), whose order is the order of (p, q); E < the
+ * number of contacts < 4 n <= 2^32, so E fits uint32; and 0xFFFFFFFF is no
+ * valid contact (the last pixel has no down-right neighbour), so it can mark
+ * "none yet".
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 4 B per 1024 pixels + 4 B, and a
+ * hash table of S slots of 16 B (24 B with d_step), S = the power of two
+ * >= 2 * Hd, at least 1024.  Hd ("heads") is counted first and read back by
+ * the host: per direction, the runs of equal id pairs along 64 consecutive
+ * pixels; E <= Hd <= the number of contacts.  A smooth frame has few; a map
+ * where every contact is its own edge (noise) has Hd ~ 4 n, i.e. up to
+ * 8 n slots. */
+#define DQ_HIP_ADJACENCY_MAX_PIXELS 0x40000000u
+int64_t dq_hip_region_adjacency_dev(int device, const uint32_t *d_regions,
+                                    uint32_t width, uint32_t height, int connectivity,
+                                    uint32_t edge_cap, uint32_t *d_edges /*2 per edge: a, b*/,
+                                    uint32_t *d_border, uint32_t *d_contact /*2 per edge: p, q*/,
+                                    const uint32_t *d_pixels, uint64_t *d_step,
+                                    uint32_t nregions, uint32_t *d_degree, void *stream);
+/* Host pointers, the current device. */
+int64_t dq_hip_region_adjacency(const uint32_t *regions, uint32_t width, uint32_t height,
+                                int connectivity, uint32_t edge_cap, uint32_t *edges,
+                                uint32_t *border, uint32_t *contact,
+                                const uint32_t *pixels, uint64_t *step,
+                                uint32_t nregions, uint32_t *degree);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
