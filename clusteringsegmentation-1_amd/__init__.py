@@ -23,6 +23,9 @@ numbered in raster order) with area, bounding box, first pixel, colour sums:
 Adjacency graph of a region map (the pairs of ids that touch, numbered in
 raster order of their first contact) with border, first contact, colour step:
     region_adjacency_device, region_adjacency
+Region merge over that graph (small regions join their most alike neighbour in
+rounds, exact integers) and the whole labels -> segments pipeline on the device:
+    merge_regions_device, segment_labels
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -97,6 +100,11 @@ def lib():
                                          c.c_uint32, vp, vp], c.c_int64),
         "dq_hip_region_adjacency": ([vp, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, vp, vp, vp, vp, vp, c.c_uint32,
                                      vp], c.c_int64),
+        "dq_hip_merge_regions_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp, c.c_uint32, vp, c.c_uint32,
+                                      c.c_uint32, c.c_uint32, vp, vp, c.c_uint32, vp, vp, vp, vp, u32p, vp],
+                                     c.c_int64),
+        "dq_hip_segment_labels": ([vp, c.c_int, c.c_uint32, c.c_uint32, c.c_int, vp, c.c_uint32, c.c_uint32,
+                                   c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, u32p], c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -784,6 +792,153 @@ def region_adjacency(regions2d, connectivity=8, pixels=None, num_regions=None):
         raise DivQuantError("dq_hip_region_adjacency: %d edges, then %d" % (e, e2))
     g["degree"] = degree
     return g
+
+
+# ---------------------------------------------------------------------------
+# Region merge over the adjacency graph (include/dq_hip.h, "region merge"):
+# components under min_area join their most alike neighbour (8.8 fixed-point
+# mean colour, ties to the lowest id) in Boruvka-style rounds; the result is
+# numbered by first pixel.  Exact integers, independent of scheduling.
+MERGE_MAX_PIXELS = (1 << 31) - 1
+NO_DISTANCE_LIMIT = 0xFFFFFFFF
+
+
+def _elems(t, count, size, what):
+    """A contiguous tensor / array of at least `count` elements of `size` bytes."""
+    if isinstance(t, np.ndarray):
+        have, contiguous, length = t.itemsize, t.flags.c_contiguous, t.size
+    elif hasattr(t, "element_size"):
+        have, contiguous, length = t.element_size(), t.is_contiguous(), t.numel()
+    else:
+        raise ValueError("%s: a tensor or an array" % what)
+    if have != size:
+        raise ValueError("%s: %d-byte elements, not %d" % (what, size, have))
+    if not contiguous:
+        raise ValueError("%s is not contiguous" % what)
+    if length < count:
+        raise ValueError("%s holds %d elements, %d are needed" % (what, length, count))
+
+
+def _scalar32(v, what):
+    v = int(v)
+    if not 0 <= v <= 0xFFFFFFFF:
+        raise ValueError("%s %d is not a uint32" % (what, v))
+    return v
+
+
+def merge_regions_device(t_regions, num_regions, t_area, t_first, t_sums, t_edges, min_area,
+                         max_dist=NO_DISTANCE_LIMIT, max_rounds=0, t_bbox=None, num_edges=None, t_out_regions=None,
+                         stats_capacity=0, with_remap=True, n=None, device=0, stream=None):
+    """Merges the regions of a device-resident id map over their adjacency
+    graph.  t_regions: n ids < num_regions (contiguous, 4-byte elements; n
+    defaults to its length); t_area, t_first (num_regions words), t_sums
+    (num_regions x 3, 8-byte elements) and optionally t_bbox (num_regions x 4
+    words) as label_regions_device gives them; t_edges: num_edges x 2 ids
+    (num_edges defaults to its length / 2; None with no edge).
+    t_out_regions=None relabels t_regions in place.  Returns (R', rounds, out):
+    out["regions"] the relabelled map, out["remap"] (num_regions,) the new id
+    of every old region (unless with_remap=False) and the first
+    min(R', stats_capacity) new regions' "area", "first", "sums" (int64) and,
+    with t_bbox, "bbox" -- none of them at capacity 0.  Synchronous.
+    ValueError for bad tensors, lengths or scalars (nothing runs)."""
+    _elems(t_regions, 0, 4, "t_regions")     # (tensors only: the lengths are checked against them)
+    if n is None:
+        n = t_regions.size if isinstance(t_regions, np.ndarray) else t_regions.numel()
+    n, nreg = int(n), int(num_regions)
+    if not 1 <= n <= MERGE_MAX_PIXELS:
+        raise ValueError("%d pixels: 1 .. 2^31 - 1" % n)
+    if not 1 <= nreg <= n:
+        raise ValueError("num_regions %d for %d pixels" % (nreg, n))
+    _elems(t_regions, n, 4, "t_regions")
+    _elems(t_area, nreg, 4, "t_area")
+    _elems(t_first, nreg, 4, "t_first")
+    _elems(t_sums, 3 * nreg, 8, "t_sums")
+    if t_bbox is not None:
+        _elems(t_bbox, 4 * nreg, 4, "t_bbox")
+    if num_edges is None:
+        if t_edges is not None:
+            _elems(t_edges, 0, 4, "t_edges")
+        num_edges = 0 if t_edges is None else (t_edges.size if isinstance(t_edges, np.ndarray) else t_edges.numel()) // 2
+    nedges = _scalar32(num_edges, "num_edges")
+    if nedges:
+        if t_edges is None:
+            raise ValueError("%d edges without t_edges" % nedges)
+        _elems(t_edges, 2 * nedges, 4, "t_edges")
+    if t_out_regions is None:
+        t_out_regions = t_regions
+    else:
+        _elems(t_out_regions, n, 4, "t_out_regions")
+    min_area, max_dist = _scalar32(min_area, "min_area"), _scalar32(max_dist, "max_dist")
+    max_rounds, cap = _scalar32(max_rounds, "max_rounds"), _scalar32(stats_capacity, "stats_capacity")
+    out = {"regions": t_out_regions}
+    st = {}
+    if cap or with_remap:
+        import torch
+        dev = f"cuda:{device}"
+        if with_remap:
+            out["remap"] = torch.empty(nreg, dtype=torch.int32, device=dev)
+        if cap:
+            st = {"area": torch.empty(cap, dtype=torch.int32, device=dev),
+                  "first": torch.empty(cap, dtype=torch.int32, device=dev),
+                  "sums": torch.empty((cap, 3), dtype=torch.int64, device=dev)}
+            if t_bbox is not None:
+                st["bbox"] = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    opt = lambda d, name: _dptr(d[name]) if name in d else None  # noqa: E731
+    rounds = ctypes.c_uint32(0)
+    r = lib().dq_hip_merge_regions_dev(device, _dptr(t_regions), n, nreg, _dptr(t_area), _dptr(t_first), _dptr(t_sums),
+                                       _dptr(t_bbox) if t_bbox is not None else None, nedges,
+                                       _dptr(t_edges) if nedges else None, min_area, max_dist, max_rounds,
+                                       _dptr(t_out_regions), opt(out, "remap"), cap, opt(st, "area"), opt(st, "bbox"),
+                                       opt(st, "first"), opt(st, "sums"), ctypes.byref(rounds), _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_merge_regions_dev: bad arguments")
+    out.update({k: v[:min(int(r), cap)] for k, v in st.items()})
+    return int(r), int(rounds.value), out
+
+
+def segment_labels(labels2d, pixels, min_area, max_dist=NO_DISTANCE_LIMIT, connectivity=8, max_rounds=0,
+                   stats_capacity=1 << 16):
+    """Segments of a host (H, W) label map of 1-, 2- or 4-byte integers and
+    its frame (H * W packed 0x00RRGGBB words): connected regions, their
+    adjacency graph and the merge, all on the device between one upload and one
+    download.  Returns (regions2d, stats, rounds): regions2d (H, W) uint32 with
+    R' segments numbered by first pixel, stats a dict of numpy arrays sized to
+    R' -- "area" (R',), "bbox" (R', 4: x0, y0, x1, y1 inclusive), "first"
+    (R',), all uint32, "sums" (R', 3) uint64 -- and the rounds counted.
+    stats_capacity: the segments the first call has room for (48 B each on the
+    host); a frame that ends with more is run once more with room for all."""
+    lab = np.asarray(labels2d)
+    if lab.ndim != 2 or lab.size == 0:
+        raise ValueError("labels2d must be a non-empty (H, W) array")
+    if lab.dtype.kind not in "ui" or lab.dtype.itemsize not in (1, 2, 4):
+        raise ValueError("labels are 1-, 2- or 4-byte integers, not %s" % lab.dtype)
+    lab = np.ascontiguousarray(lab)
+    h, w = lab.shape
+    _adjacency_shape(w, h, connectivity)
+    if pixels is None:
+        raise ValueError("the frame is needed: the merge compares mean colours")
+    px = _u32(pixels).reshape(-1)
+    if px.size != lab.size:
+        raise ValueError("%d pixels for %d labels" % (px.size, lab.size))
+    min_area, max_dist = _scalar32(min_area, "min_area"), _scalar32(max_dist, "max_dist")
+    max_rounds, cap = _scalar32(max_rounds, "max_rounds"), _scalar32(stats_capacity, "stats_capacity")
+    if cap < 1:
+        raise ValueError("stats_capacity is at least 1")
+    _require_gpu()
+    regions = np.zeros((h, w), np.uint32)
+    rounds = ctypes.c_uint32(0)
+    cap = min(cap, lab.size)
+    while True:     # (R' is not known before the call: at most one more call, with room for R')
+        st = {"area": np.zeros(cap, np.uint32), "bbox": np.zeros((cap, 4), np.uint32),
+              "first": np.zeros(cap, np.uint32), "sums": np.zeros((cap, 3), np.uint64)}
+        r = lib().dq_hip_segment_labels(_ptr(lab), lab.dtype.itemsize, w, h, connectivity, _ptr(px), min_area,
+                                        max_dist, max_rounds, _ptr(regions), cap, _ptr(st["area"]), _ptr(st["bbox"]),
+                                        _ptr(st["first"]), _ptr(st["sums"]), ctypes.byref(rounds))
+        if r < 0:
+            raise DivQuantError("dq_hip_segment_labels: bad arguments")
+        if r <= cap:
+            return regions, {k: v[:r].copy() for k, v in st.items()}, int(rounds.value)
+        cap = int(r)
 
 
 # ---------------------------------------------------------------------------

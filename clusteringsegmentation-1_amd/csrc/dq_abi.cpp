@@ -24,6 +24,7 @@
 #include "../../include/quant_util.h"
 #include "dq_engine.h"
 #include "dq_adjacency.h"
+#include "dq_merge.h"
 #include "dq_regions.h"
 #include "dq_weighted.h"
 
@@ -1063,6 +1064,138 @@ int64_t dq_hip_region_adjacency(const uint32_t* regions, uint32_t width, uint32_
   DQ_HIP(hipStreamSynchronize(st));
   for (void* p : {(void*)d_regions, (void*)d_edges, (void*)d_border, (void*)d_contact, (void*)d_pixels,
                   (void*)d_step, (void*)d_degree})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return count;
+}
+
+// Region merge over the adjacency graph (dq_merge.hip).  Every argument check
+// comes before the first HIP call.
+static bool merge_args_ok(const uint32_t* regions, uint32_t n, uint32_t nregions, const uint32_t* area,
+                          const uint32_t* first, const uint64_t* sums, const uint32_t* bbox, uint32_t nedges,
+                          const uint32_t* edges, const uint32_t* out_regions, const uint32_t* remap,
+                          uint32_t stats_cap, const uint32_t* out_area, const uint32_t* out_bbox,
+                          const uint32_t* out_first, const uint64_t* out_sums) {
+  if (!regions || !area || !first || !sums || !out_regions) return false;
+  if (n == 0 || n > 0x7FFFFFFFu) return false;
+  if (nregions == 0 || nregions > n) return false;
+  if (nedges > 0 && !edges) return false;
+  for (const void* p : {(const void*)regions, (const void*)area, (const void*)first, (const void*)bbox,
+                        (const void*)edges, (const void*)out_regions, (const void*)remap, (const void*)out_area,
+                        (const void*)out_bbox, (const void*)out_first})
+    if (((uintptr_t)p & 3u) != 0) return false;
+  if (((uintptr_t)sums & 7u) != 0 || ((uintptr_t)out_sums & 7u) != 0) return false;
+  if (out_bbox && !bbox) return false;
+  if (stats_cap > 0 && !out_area && !out_bbox && !out_first && !out_sums) return false;
+  return true;
+}
+
+// Enqueues the rounds on st with scratch owned by the call, waits, returns R'.
+// The host reads the links of a round back (4 bytes) and stops at 0.
+static int64_t merge_regions_on(hipStream_t st, dq::MergeArgs a, uint32_t max_rounds, uint32_t* rounds) {
+  DQ_HIP(hipMallocAsync(&a.scratch, dq::merge_scratch_bytes(a.n, a.nregions, a.bbox != nullptr, a.remap != nullptr),
+                        st));
+  dq::launch_merge_init(a, st);
+  uint32_t done = 0;
+  // Every counted round makes a link, i.e. removes at least one component: fewer than nregions rounds,
+  // so the loop ends by itself.  (Without a distance limit the restless components at least halve per
+  // round; with one, a component may get its first offer only after a neighbour's mean has moved, and
+  // a star of such leaves takes a round per leaf.)
+  while (a.nedges != 0 && a.min_area != 0 && (max_rounds == 0 || done < max_rounds)) {
+    dq::launch_merge_choose(a, st);
+    DQ_HIP(hipGetLastError());
+    uint32_t links = 0;
+    DQ_HIP(hipMemcpyAsync(&links, dq::merge_links_word(a), 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+    if (links == 0) break;
+    dq::launch_merge_fold(a, st);
+    ++done;
+  }
+  DQ_HIP(dq::launch_merge_finish(a, st));
+  DQ_HIP(hipGetLastError());
+  uint32_t count = 0;
+  DQ_HIP(hipMemcpyAsync(&count, dq::merge_count_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipFreeAsync(a.scratch, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  if (rounds) *rounds = done;
+  return (int64_t)count;
+}
+
+int64_t dq_hip_merge_regions_dev(int device, const uint32_t* d_regions, uint32_t n, uint32_t nregions,
+                                 const uint32_t* d_area, const uint32_t* d_first, const uint64_t* d_sums,
+                                 const uint32_t* d_bbox, uint32_t nedges, const uint32_t* d_edges, uint32_t min_area,
+                                 uint32_t max_dist, uint32_t max_rounds, uint32_t* d_out_regions, uint32_t* d_remap,
+                                 uint32_t stats_cap, uint32_t* d_out_area, uint32_t* d_out_bbox,
+                                 uint32_t* d_out_first, uint64_t* d_out_sums, uint32_t* rounds, void* stream) {
+  if (!merge_args_ok(d_regions, n, nregions, d_area, d_first, d_sums, d_bbox, nedges, d_edges, d_out_regions, d_remap,
+                     stats_cap, d_out_area, d_out_bbox, d_out_first, d_out_sums))
+    return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  dq::MergeArgs a{d_regions, n,        nregions,      d_area,  d_first,   (const unsigned long long*)d_sums,
+                  d_bbox,    nedges,   d_edges,       min_area, max_dist, d_out_regions,
+                  d_remap,   stats_cap, d_out_area,   d_out_bbox, d_out_first, (unsigned long long*)d_out_sums,
+                  nullptr};
+  return merge_regions_on(st, a, max_rounds, rounds);
+}
+
+int64_t dq_hip_segment_labels(const void* labels, int label_bytes, uint32_t width, uint32_t height, int connectivity,
+                              const uint32_t* pixels, uint32_t min_area, uint32_t max_dist, uint32_t max_rounds,
+                              uint32_t* regions, uint32_t stats_cap, uint32_t* area, uint32_t* bbox, uint32_t* first,
+                              uint64_t* sums, uint32_t* rounds) {
+  if (!pixels ||
+      !regions_args_ok(labels, label_bytes, width, height, connectivity, regions, stats_cap, area, bbox, first,
+                       nullptr, pixels, sums) ||
+      !adjacency_args_ok(regions, width, height, connectivity, 0, nullptr, nullptr, nullptr, pixels, nullptr, 0,
+                         nullptr))
+    return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height;
+  void* d_labels = nullptr;
+  uint32_t *d_pixels = nullptr, *d_regions = nullptr, *d_area = nullptr, *d_first = nullptr, *d_bbox = nullptr,
+           *d_edges = nullptr, *o_area = nullptr, *o_bbox = nullptr, *o_first = nullptr;
+  uint64_t *d_sums = nullptr, *o_sums = nullptr;
+  DQ_HIP(hipMallocAsync(&d_labels, n * (size_t)label_bytes, st));
+  DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
+  DQ_HIP(hipMemcpyAsync(d_labels, labels, n * (size_t)label_bytes, hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
+  // R and E are known only after their stages ran: count-only, then with exact capacity
+  const int64_t R = label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions, 0, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr, nullptr);
+  DQ_HIP(hipMallocAsync((void**)&d_area, (size_t)R * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_first, (size_t)R * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_sums, (size_t)R * 24, st));
+  if (stats_cap && bbox) DQ_HIP(hipMallocAsync((void**)&d_bbox, (size_t)R * 16, st));
+  label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions, (uint32_t)R, d_area, d_bbox,
+                   d_first, nullptr, d_pixels, d_sums);
+  const int64_t E = region_adjacency_on(st, d_regions, width, height, connectivity, 0, nullptr, nullptr, nullptr,
+                                        nullptr, nullptr, 0, nullptr);
+  if (E > 0) {
+    DQ_HIP(hipMallocAsync((void**)&d_edges, (size_t)E * 8, st));
+    region_adjacency_on(st, d_regions, width, height, connectivity, (uint32_t)E, d_edges, nullptr, nullptr, nullptr,
+                        nullptr, 0, nullptr);
+  }
+  const size_t cap = std::min((size_t)stats_cap, (size_t)R);   // (R' <= R)
+  if (cap && area) DQ_HIP(hipMallocAsync((void**)&o_area, cap * 4, st));
+  if (cap && bbox) DQ_HIP(hipMallocAsync((void**)&o_bbox, cap * 16, st));
+  if (cap && first) DQ_HIP(hipMallocAsync((void**)&o_first, cap * 4, st));
+  if (cap && sums) DQ_HIP(hipMallocAsync((void**)&o_sums, cap * 24, st));
+  dq::MergeArgs a{d_regions, (uint32_t)n,   (uint32_t)R, d_area,   d_first,  (const unsigned long long*)d_sums,
+                  d_bbox,    (uint32_t)E,   d_edges,     min_area, max_dist, d_regions,
+                  nullptr,   (uint32_t)cap, o_area,      o_bbox,   o_first,  (unsigned long long*)o_sums,
+                  nullptr};
+  const int64_t count = merge_regions_on(st, a, max_rounds, rounds);
+  // nothing behind entry min(R', stats_cap) is written
+  const size_t m = std::min((size_t)count, cap);
+  DQ_HIP(hipMemcpyAsync(regions, d_regions, n * 4, hipMemcpyDeviceToHost, st));
+  if (o_area && m) DQ_HIP(hipMemcpyAsync(area, o_area, m * 4, hipMemcpyDeviceToHost, st));
+  if (o_bbox && m) DQ_HIP(hipMemcpyAsync(bbox, o_bbox, m * 16, hipMemcpyDeviceToHost, st));
+  if (o_first && m) DQ_HIP(hipMemcpyAsync(first, o_first, m * 4, hipMemcpyDeviceToHost, st));
+  if (o_sums && m) DQ_HIP(hipMemcpyAsync(sums, o_sums, m * 24, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  for (void* p : {d_labels, (void*)d_pixels, (void*)d_regions, (void*)d_area, (void*)d_first, (void*)d_bbox,
+                  (void*)d_edges, (void*)d_sums, (void*)o_area, (void*)o_bbox, (void*)o_first, (void*)o_sums})
     if (p) DQ_HIP(hipFreeAsync(p, st));
   return count;
 }

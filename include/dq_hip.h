@@ -331,6 +331,91 @@ int64_t dq_hip_region_adjacency(const uint32_t *regions, uint32_t width, uint32_
                                 const uint32_t *pixels, uint64_t *step,
                                 uint32_t nregions, uint32_t *degree);
 
+/* ---- region merge (regions + their graph -> segments, on the device) ------
+ * Connected regions of a cluster-label map are mostly specks; the reference
+ * absorbs them with sequential heuristics (mergeSmallSuperpixels: superpixels
+ * under 10 pixels go to their most alike neighbour).  These entries merge over
+ * the adjacency graph by a rule with ONE exact integer answer that does not
+ * depend on scheduling (Boruvka-style rounds).
+ * Inputs.  A flat map of n uint32 region ids, each < nregions = R.  Per region
+ * d_area[r] > 0, d_first[r] (its lowest pixel index, distinct per region) and
+ * d_sums[r][3] (uint64 R, G, B sums): the arrays dq_hip_label_regions_dev
+ * writes; optionally d_bbox[r][4].  A list of nedges id pairs (a, b), a != b,
+ * both < R: the order within a pair, the order of the pairs and duplicates do
+ * not matter (the d_edges of dq_hip_region_adjacency_dev is the intended one).
+ * State.  comp[r], the component of region r, at first r itself.  A component
+ * carries area, sums, first and bbox of its regions together.
+ * One round.
+ *   1 A component A is restless when area[A] < min_area.
+ *   2 mean(A, c) = floor(256 * sums[A][c] / area[A]), integer, < 2^16.
+ *   3 d(A, B) = the sum over c of |mean(A, c) - mean(B, c)| (<= 195840).
+ *   4 Every edge with A = comp[a] != B = comp[b] and d(A, B) <= max_dist
+ *     offers A, if restless, the key (d << 32) | B, and B, if restless, the
+ *     key (d << 32) | A.  best[A] is the lowest key offered to A: the lowest
+ *     distance, ties to the lowest component id.
+ *   5 A restless A with a best has the target T = the low word of best[A].
+ *     If T is restless, best[T] targets A and A < T, A stays a root;
+ *     otherwise parent[A] = T.
+ *   6 A round that makes no link is not counted and ends the call.
+ *   7 Otherwise the root of a component is the fixed point of parent; area,
+ *     sums, the minimum first and the bbox union of every component are added
+ *     into its root, comp[r] = root(comp[r]) for every r, and the round counts.
+ *   (Along a cycle of parent choices the distances cannot increase, so they
+ *   are equal; among equal distances everyone picks its lowest neighbour, so
+ *   the node after the cycle's lowest id points back at it: a mutual pair, of
+ *   which rule 5 keeps the lower as the root.  parent is a forest.)
+ * End.  After a round without a link, or after max_rounds rounds (0: no
+ * limit).  Every counted round removes at least one component, so there are
+ * fewer than nregions rounds.  With max_dist = 0xFFFFFFFF the restless
+ * components at least halve per round (32 rounds at most); with a distance
+ * limit a component may get its first offer only after a neighbour's mean has
+ * moved, and a star of such leaves takes one round per leaf.  The final
+ * components are numbered 0 .. R'-1 in increasing order of their first, the
+ * numbering rule of the connected regions above.
+ * Outputs.  d_out_regions (required, may be d_regions): the n new ids.
+ * d_remap (may be NULL): nregions words, the new id of old region r.  Stats of
+ * the new regions (each pointer may be NULL), stats_cap entries each, regions
+ * with new id >= stats_cap left out and nothing behind entry min(R', stats_cap)
+ * written: d_out_area, d_out_bbox (4 words; needs d_bbox), d_out_first,
+ * d_out_sums (3 uint64).  *rounds (host, may be NULL): the rounds counted.
+ * nedges == 0 or min_area == 0 is a valid call that only renumbers by first.
+ * Returns R' >= 1, synchronous on return.  -1, before any device work, for:
+ * NULL d_regions, d_area, d_first, d_sums or d_out_regions; n == 0 or n above
+ * 2^31 - 1; nregions == 0 or above n; nedges > 0 with NULL d_edges; a pointer
+ * not naturally aligned (4 B; 8 B for the sums); d_out_bbox without d_bbox;
+ * stats_cap > 0 with every output stats pointer NULL.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 60 B per region (76 B with
+ * d_bbox, 4 B more without d_remap), one bit per pixel and 4 B per 1024
+ * pixels.  The host reads 4 bytes back per round (the links made). */
+int64_t dq_hip_merge_regions_dev(int device, const uint32_t *d_regions, uint32_t n,
+                                 uint32_t nregions, const uint32_t *d_area,
+                                 const uint32_t *d_first, const uint64_t *d_sums,
+                                 const uint32_t *d_bbox /*may be NULL*/,
+                                 uint32_t nedges, const uint32_t *d_edges /*2 per edge*/,
+                                 uint32_t min_area, uint32_t max_dist, uint32_t max_rounds,
+                                 uint32_t *d_out_regions /*may equal d_regions*/,
+                                 uint32_t *d_remap /*may be NULL*/,
+                                 uint32_t stats_cap, uint32_t *d_out_area, uint32_t *d_out_bbox,
+                                 uint32_t *d_out_first, uint64_t *d_out_sums,
+                                 uint32_t *rounds /*host, may be NULL*/, void *stream);
+/* Host labels -> segments, the current device: one upload (labels and the
+ * packed 0x00RRGGBB frame), connected regions, their adjacency graph and the
+ * merge above on the device, one download (the map and the stats of the R'
+ * segments; bbox x0, y0, x1, y1 inclusive).  The region and edge counts are
+ * known only after those stages ran, so each of the two runs twice: count-only,
+ * then with exact capacity.  Returns R'; -1, before any device work, for what
+ * dq_hip_label_regions or dq_hip_region_adjacency refuse (label_bytes,
+ * connectivity, sides above 65535, more than DQ_HIP_ADJACENCY_MAX_PIXELS
+ * pixels, NULL or misaligned labels / regions / stats arrays, stats_cap > 0
+ * with every stats pointer NULL) and for NULL pixels. */
+int64_t dq_hip_segment_labels(const void *labels, int label_bytes, uint32_t width,
+                              uint32_t height, int connectivity, const uint32_t *pixels,
+                              uint32_t min_area, uint32_t max_dist, uint32_t max_rounds,
+                              uint32_t *regions, uint32_t stats_cap, uint32_t *area,
+                              uint32_t *bbox, uint32_t *first, uint64_t *sums,
+                              uint32_t *rounds /*may be NULL*/);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
