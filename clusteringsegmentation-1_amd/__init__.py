@@ -26,6 +26,10 @@ raster order of their first contact) with border, first contact, colour step:
 Region merge over that graph (small regions join their most alike neighbour in
 rounds, exact integers) and the whole labels -> segments pipeline on the device:
     merge_regions_device, segment_labels
+Pixel lists of a region map (stable counting sort by id: offsets, indexes,
+Coords, colours), their inverse and region map -> per-region quant -> frame:
+    region_pixels_device, region_pixels, scatter_coords_device,
+    quant_region_map_device, quant_region_map
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -105,6 +109,14 @@ def lib():
                                      c.c_int64),
         "dq_hip_segment_labels": ([vp, c.c_int, c.c_uint32, c.c_uint32, c.c_int, vp, c.c_uint32, c.c_uint32,
                                    c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, u32p], c.c_int64),
+        "dq_hip_region_pixels_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp, vp],
+                                     c.c_int64),
+        "dq_hip_region_pixels": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp], c.c_int64),
+        "dq_hip_scatter_coords_dev": ([c.c_int, vp, vp, c.c_uint32, c.c_uint32, vp, vp], c.c_int),
+        "dq_hip_quant_region_map_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp, vp, vp,
+                                         c.c_int, vp], c.c_int64),
+        "dq_hip_quant_region_map": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp, vp, vp, c.c_int],
+                                    c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -939,6 +951,190 @@ def segment_labels(labels2d, pixels, min_area, max_dist=NO_DISTANCE_LIMIT, conne
         if r <= cap:
             return regions, {k: v[:r].copy() for k, v in st.items()}, int(rounds.value)
         cap = int(r)
+
+
+# ---------------------------------------------------------------------------
+# Pixel lists of a region map (include/dq_hip.h, "pixel lists"): the stable
+# counting sort of the pixels by region id, as offsets (CSR) plus the pixel
+# indexes, Coord words and frame words in that order; its inverse; and the
+# region map -> per-region quant -> painted frame pipeline on top of them.
+# Exact integers, independent of scheduling.
+PIXELS_MAX_PIXELS = (1 << 31) - 1
+PIXELS_MAX_REGIONS = (1 << 31) - 1
+
+
+class RegionRowsError(DivQuantError):
+    """The library's -2: the ids of the map span more rows in total than the
+    map has pixels (never so for connected regions)."""
+
+
+def _pixels_shape(width, height, num_regions):
+    width, height, nreg = int(width), int(height), int(num_regions)
+    if not (1 <= width <= REGION_MAX_SIDE and 1 <= height <= REGION_MAX_SIDE) or width * height > PIXELS_MAX_PIXELS:
+        raise ValueError("a %d x %d map: sides are 1..65535, at most 2^31 - 1 pixels" % (width, height))
+    if not 1 <= nreg <= PIXELS_MAX_REGIONS:
+        raise ValueError("num_regions %d: 1 .. 2^31 - 1" % nreg)
+    return width, height, nreg
+
+
+def _pixels_result(r, name):
+    if r == -2:
+        raise RegionRowsError("%s: the ids span more rows in total than the map has pixels" % name)
+    if r < 0:
+        raise DivQuantError("%s: bad arguments" % name)
+    return int(r)
+
+
+def region_pixels_device(t_regions, width, height, num_regions, t_offsets, t_coords=None, t_index=None,
+                         t_pixels=None, t_colors=None, device=0, stream=None):
+    """The pixel lists of a device-resident width x height map of region ids
+    (< num_regions each; contiguous, 4-byte elements).  t_offsets gets
+    num_regions + 1 words: t_offsets[r] = the pixels with an id < r.  Each of
+    t_coords (x | y << 16), t_index (y * width + x) and t_colors (t_pixels
+    there; needs t_pixels), width * height words, is filled when given: region
+    r's pixels in raster order at [t_offsets[r], t_offsets[r + 1]).
+    Synchronous.  ValueError for bad tensors or shapes (nothing runs),
+    RegionRowsError when the library refuses the map (nothing is written)."""
+    width, height, nreg = _pixels_shape(width, height, num_regions)
+    n = width * height
+    _elems(t_regions, n, 4, "t_regions")
+    _elems(t_offsets, nreg + 1, 4, "t_offsets")
+    for t, what in ((t_coords, "t_coords"), (t_index, "t_index"), (t_pixels, "t_pixels"), (t_colors, "t_colors")):
+        if t is not None:
+            _elems(t, n, 4, what)
+    if t_colors is not None and t_pixels is None:
+        raise ValueError("t_colors without t_pixels")
+    opt = lambda t: _dptr(t) if t is not None else None  # noqa: E731
+    r = lib().dq_hip_region_pixels_dev(device, _dptr(t_regions), width, height, nreg, _dptr(t_offsets), opt(t_coords),
+                                       opt(t_index), opt(t_pixels), opt(t_colors), _stream_ptr(stream))
+    _pixels_result(r, "dq_hip_region_pixels_dev")
+
+
+def _region_map(regions2d, num_regions):
+    """A host (H, W) map of ids as contiguous uint32, and its id count."""
+    reg = np.asarray(regions2d)
+    if reg.ndim != 2 or reg.size == 0:
+        raise ValueError("regions2d must be a non-empty (H, W) array")
+    if reg.dtype.kind not in "ui" or reg.dtype.itemsize > 4:
+        raise ValueError("region ids are integers of at most 4 bytes, not %s" % reg.dtype)
+    if reg.dtype.kind == "i" and reg.min() < 0:
+        raise ValueError("region ids are not negative")
+    reg = _u32(reg)
+    top = int(reg.max())
+    nreg = top + 1 if num_regions is None else int(num_regions)
+    if not top < nreg:
+        raise ValueError("num_regions %d for ids up to %d" % (nreg, top))
+    _pixels_shape(reg.shape[1], reg.shape[0], nreg)
+    return reg, nreg
+
+
+def region_pixels(regions2d, num_regions=None, pixels=None):
+    """The pixel lists of a host (H, W) map of region ids (integers of at most
+    4 bytes; num_regions=None takes regions2d.max() + 1).  Returns (offsets,
+    index, coords, colours), uint32: offsets (num_regions + 1,), and per pixel
+    in list order its index y * W + x, its Coord word x | y << 16 and, with
+    pixels (H * W words), its frame word (None without)."""
+    reg, nreg = _region_map(regions2d, num_regions)
+    h, w = reg.shape
+    px = None
+    if pixels is not None:
+        px = _u32(pixels).reshape(-1)
+        if px.size != reg.size:
+            raise ValueError("%d pixels for %d region ids" % (px.size, reg.size))
+    _require_gpu()
+    offsets = np.zeros(nreg + 1, np.uint32)
+    index, coords = np.zeros(reg.size, np.uint32), np.zeros(reg.size, np.uint32)
+    colours = np.zeros(reg.size, np.uint32) if px is not None else None
+    r = lib().dq_hip_region_pixels(_ptr(reg), w, h, nreg, _ptr(offsets), _ptr(coords), _ptr(index),
+                                   _ptr(px) if px is not None else None,
+                                   _ptr(colours) if px is not None else None)
+    _pixels_result(r, "dq_hip_region_pixels")
+    return offsets, index, coords, colours
+
+
+def scatter_coords_device(t_values, t_coords, n, width, t_frame, device=0, stream=None):
+    """t_frame[(c >> 16) * width + (c & 0xFFFF)] = t_values[i] for the n Coord
+    words c = t_coords[i] (the inverse of a gather by Coords), asynchronous.
+    Coords are not range-checked.  ValueError for bad tensors or scalars."""
+    n, width = _scalar32(n, "n"), int(width)
+    if not 1 <= width <= REGION_MAX_SIDE:
+        raise ValueError("width %d: 1 .. 65535" % width)
+    _elems(t_values, n, 4, "t_values")
+    _elems(t_coords, n, 4, "t_coords")
+    _elems(t_frame, min(n, 1), 4, "t_frame")
+    if lib().dq_hip_scatter_coords_dev(device, _dptr(t_values), _dptr(t_coords), n, width, _dptr(t_frame),
+                                       _stream_ptr(stream)) < 0:
+        raise DivQuantError("dq_hip_scatter_coords_dev: bad arguments")
+
+
+def _region_map_tables(nreg, k, cts, k_outs):
+    """The host colortable rows and sizes of a region-map call (given: filled in place)."""
+    if cts is None:
+        cts = np.zeros((nreg, k), np.uint32)
+    elif not (isinstance(cts, np.ndarray) and cts.dtype == np.uint32 and cts.flags.c_contiguous and cts.size >= nreg * k):
+        raise ValueError("cts: a contiguous uint32 array of num_regions * num_clusters entries")
+    if k_outs is None:
+        k_outs = np.zeros(nreg, np.uint32)
+    elif not (isinstance(k_outs, np.ndarray) and k_outs.dtype == np.uint32 and k_outs.flags.c_contiguous
+              and k_outs.size >= nreg):
+        raise ValueError("k_outs: a contiguous uint32 array of num_regions entries")
+    return cts, k_outs
+
+
+def _region_map_scalars(num_clusters, max_iters):
+    k, max_iters = int(num_clusters), int(max_iters)
+    if not 1 <= k <= 0x7FFFFFFF:
+        raise ValueError("num_clusters %d" % k)
+    if not 1 <= max_iters <= 0x7FFFFFFF:
+        raise ValueError("max_iters %d" % max_iters)
+    return k, max_iters
+
+
+def quant_region_map_device(t_regions, width, height, num_regions, t_pixels, num_clusters, t_out=None, max_iters=10,
+                            cts=None, k_outs=None, device=0, stream=None):
+    """quant_recurse(N_region, .., K, allPixelsUnique=0) of every region of a
+    device-resident region map (ClusteringSegmentation.cpp:1779-1846): the
+    pixel lists, one call of the weighted-regions path over them and, with
+    t_out (width * height words), every pixel painted with its mapped colour.
+    Returns (cts, k_outs, empty): region r's colortable is
+    cts[r, :k_outs[r]]; an id without a pixel has k_outs[r] == 0 and its row of
+    cts (zeros, or the array passed in) untouched.  Synchronous.  ValueError
+    for bad tensors, shapes or scalars (nothing runs), RegionRowsError when
+    the library refuses the map."""
+    width, height, nreg = _pixels_shape(width, height, num_regions)
+    n = width * height
+    k, max_iters = _region_map_scalars(num_clusters, max_iters)
+    _elems(t_regions, n, 4, "t_regions")
+    _elems(t_pixels, n, 4, "t_pixels")
+    if t_out is not None:
+        _elems(t_out, n, 4, "t_out")
+    cts, k_outs = _region_map_tables(nreg, k, cts, k_outs)
+    r = lib().dq_hip_quant_region_map_dev(device, _dptr(t_regions), width, height, nreg, _dptr(t_pixels), k,
+                                          _dptr(t_out) if t_out is not None else None, _ptr(cts), _ptr(k_outs),
+                                          max_iters, _stream_ptr(stream))
+    return cts, k_outs, _pixels_result(r, "dq_hip_quant_region_map_dev")
+
+
+def quant_region_map(regions2d, pixels, num_clusters, num_regions=None, max_iters=10, paint=True, cts=None,
+                     k_outs=None):
+    """quant_region_map_device on a host (H, W) map of region ids and its frame
+    (H * W packed 0x00RRGGBB words), between one upload and one download.
+    Returns (out2d, cts, k_outs, empty): out2d (H, W) uint32, the painted
+    frame (None with paint=False)."""
+    reg, nreg = _region_map(regions2d, num_regions)
+    h, w = reg.shape
+    if pixels is None:
+        raise ValueError("the frame is needed")
+    px = _u32(pixels).reshape(-1)
+    if px.size != reg.size:
+        raise ValueError("%d pixels for %d region ids" % (px.size, reg.size))
+    k, max_iters = _region_map_scalars(num_clusters, max_iters)
+    cts, k_outs = _region_map_tables(nreg, k, cts, k_outs)
+    _require_gpu()
+    out = np.zeros((h, w), np.uint32) if paint else None
+    r = lib().dq_hip_quant_region_map(_ptr(reg), w, h, nreg, _ptr(px), k, _ptr(out) if paint else None, _ptr(cts),
+                                      _ptr(k_outs), max_iters)
+    return out, cts, k_outs, _pixels_result(r, "dq_hip_quant_region_map")
 
 
 # ---------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "dq_engine.h"
 #include "dq_adjacency.h"
 #include "dq_merge.h"
+#include "dq_pixels.h"
 #include "dq_regions.h"
 #include "dq_weighted.h"
 
@@ -1198,6 +1199,214 @@ int64_t dq_hip_segment_labels(const void* labels, int label_bytes, uint32_t widt
                   (void*)d_edges, (void*)d_sums, (void*)o_area, (void*)o_bbox, (void*)o_first, (void*)o_sums})
     if (p) DQ_HIP(hipFreeAsync(p, st));
   return count;
+}
+
+// Pixel lists of a region map (dq_pixels.hip).  Every argument check comes
+// before the first HIP call.
+static bool pixels_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                           const uint32_t* offsets, const uint32_t* coords, const uint32_t* index,
+                           const uint32_t* pixels, const uint32_t* colors) {
+  if (!regions || !offsets) return false;
+  if (width == 0 || height == 0 || width > 65535u || height > 65535u || (uint64_t)width * height > 0x7FFFFFFFull)
+    return false;
+  if (nregions == 0 || nregions > 0x7FFFFFFFu) return false;
+  for (const void* p : {(const void*)regions, (const void*)offsets, (const void*)coords, (const void*)index,
+                        (const void*)pixels, (const void*)colors})
+    if (((uintptr_t)p & 3u) != 0) return false;
+  if (colors && !pixels) return false;
+  return true;
+}
+
+// Enqueues both halves on st with scratch owned by the call and waits.  One
+// small read-back sits between the halves: the table is sized from T, and a
+// map with T > n is refused there, before any output array is written.
+static int64_t region_pixels_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                uint32_t nregions, uint32_t* d_offsets, uint32_t* d_coords, uint32_t* d_index,
+                                const uint32_t* d_pixels, uint32_t* d_colors) {
+  dq::PixelsArgs a{d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels, d_colors, nullptr, nullptr};
+  DQ_HIP(hipMallocAsync((void**)&a.rows, dq::pixels_rows_bytes(nregions), st));
+  dq::launch_pixels_rows(a, st);
+  DQ_HIP(hipGetLastError());
+  uint32_t total = 0;
+  DQ_HIP(hipMemcpyAsync(&total, dq::pixels_total_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  const bool fits = total <= width * height;
+  if (fits) {
+    DQ_HIP(hipMallocAsync((void**)&a.table, dq::pixels_table_bytes(total), st));
+    dq::launch_pixels_lists(a, total, st);
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(hipFreeAsync(a.table, st));
+  }
+  DQ_HIP(hipFreeAsync(a.rows, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return fits ? 0 : -2;
+}
+
+int64_t dq_hip_region_pixels_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                 uint32_t nregions, uint32_t* d_offsets, uint32_t* d_coords, uint32_t* d_index,
+                                 const uint32_t* d_pixels, uint32_t* d_colors, void* stream) {
+  if (!pixels_args_ok(d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels, d_colors)) return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  return region_pixels_on(st, d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels, d_colors);
+}
+
+int64_t dq_hip_region_pixels(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                             uint32_t* offsets, uint32_t* coords, uint32_t* index, const uint32_t* pixels,
+                             uint32_t* colors) {
+  if (!pixels_args_ok(regions, width, height, nregions, offsets, coords, index, pixels, colors)) return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
+  uint32_t *d_regions = nullptr, *d_offsets = nullptr, *d_coords = nullptr, *d_index = nullptr, *d_pixels = nullptr,
+           *d_colors = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
+  if (coords) DQ_HIP(hipMallocAsync((void**)&d_coords, n * 4, st));
+  if (index) DQ_HIP(hipMallocAsync((void**)&d_index, n * 4, st));
+  if (colors) {
+    DQ_HIP(hipMallocAsync((void**)&d_colors, n * 4, st));
+    DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
+    DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
+  }
+  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
+  const int64_t rc = region_pixels_on(st, d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels,
+                                      d_colors);
+  if (rc == 0) {   // (a refused map leaves the host arrays as they were)
+    DQ_HIP(hipMemcpyAsync(offsets, d_offsets, no * 4, hipMemcpyDeviceToHost, st));
+    if (coords) DQ_HIP(hipMemcpyAsync(coords, d_coords, n * 4, hipMemcpyDeviceToHost, st));
+    if (index) DQ_HIP(hipMemcpyAsync(index, d_index, n * 4, hipMemcpyDeviceToHost, st));
+    if (colors) DQ_HIP(hipMemcpyAsync(colors, d_colors, n * 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+  }
+  for (void* p : {(void*)d_regions, (void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_pixels,
+                  (void*)d_colors})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return rc;
+}
+
+int dq_hip_scatter_coords_dev(int device, const uint32_t* d_values, const uint32_t* d_coords, uint32_t n,
+                              uint32_t width, uint32_t* d_frame, void* stream) {
+  if (!d_values || !d_coords || !d_frame || width == 0) return -1;
+  for (const void* p : {(const void*)d_values, (const void*)d_coords, (const void*)d_frame})
+    if (((uintptr_t)p & 3u) != 0) return -1;
+  if (n == 0) return 0;
+  hipStream_t st = engine_stream(device, stream);
+  dq::launch_scatter_coords(d_values, d_coords, n, width, d_frame, st);
+  join_default_stream(stream, st);
+  DQ_HIP(hipGetLastError());
+  return 0;
+}
+
+// Region map -> pixel lists -> one weighted quant per region -> painted frame.
+// The regions path keeps one pinned argument and one pinned result record per
+// job of a call (about 4.5 KB): the jobs go to it kRegionMapJobs at a time.
+static constexpr size_t kRegionMapJobs = 8192;
+
+static bool region_map_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                               const uint32_t* pixels, uint32_t k, const uint32_t* out, const uint32_t* cts,
+                               const uint32_t* k_outs, int max_iters) {
+  if (!pixels || !cts || !k_outs || k == 0 || k > 0x7FFFFFFFu || max_iters < 1) return false;
+  if (((uintptr_t)out & 3u) != 0) return false;
+  // (the offsets and lists are the call's own: any aligned non-NULL pointer stands in for them)
+  return pixels_args_ok(regions, width, height, nregions, regions, nullptr, nullptr, pixels, nullptr);
+}
+
+static int64_t quant_region_map_on(int device, hipStream_t st, const uint32_t* d_regions, uint32_t width,
+                                   uint32_t height, uint32_t nregions, const uint32_t* d_pixels, uint32_t k,
+                                   uint32_t* d_out, uint32_t* cts, uint32_t* k_outs, int max_iters) {
+  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
+  uint32_t *d_offsets = nullptr, *d_colors = nullptr, *d_coords = nullptr, *d_mapped = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_colors, n * 4, st));
+  if (d_out) {
+    DQ_HIP(hipMallocAsync((void**)&d_coords, n * 4, st));
+    DQ_HIP(hipMallocAsync((void**)&d_mapped, n * 4, st));
+    // (an id >= nregions leaves its pixel out of the lists: the scatter below then reads Coord 0, not garbage)
+    DQ_HIP(hipMemsetAsync(d_coords, 0, n * 4, st));
+  }
+  int64_t rc = region_pixels_on(st, d_regions, width, height, nregions, d_offsets, d_coords, nullptr, d_pixels, d_colors);
+  if (rc == 0) {
+    std::vector<uint32_t> off(no);
+    DQ_HIP(hipMemcpyAsync(off.data(), d_offsets, no * 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+    Engine& e = engine_for(device);
+    std::vector<dq::FrameJob> jobs;
+    std::vector<uint32_t> ids;
+    jobs.reserve(std::min<size_t>(nregions, kRegionMapJobs));
+    ids.reserve(jobs.capacity());
+    auto flush = [&] {
+      if (jobs.empty()) return;
+      {
+        std::lock_guard<std::mutex> g(e.mutex());
+        e.run_weighted_regions(jobs.data(), (int)jobs.size(), max_iters, st);
+      }
+      for (size_t i = 0; i < jobs.size(); ++i) {
+        k_outs[ids[i]] = (uint32_t)jobs[i].k_out;
+        rc += jobs[i].num_empty;
+      }
+      jobs.clear();
+      ids.clear();
+    };
+    for (uint32_t r = 0; r < nregions; ++r) {
+      const uint32_t len = off[r + 1] - off[r];
+      if (len == 0) {   // an id without a pixel: no call, its colortable row stays as it is
+        k_outs[r] = 0;
+        continue;
+      }
+      dq::FrameJob j;
+      j.d_in = d_colors + off[r];
+      j.n = len;
+      j.d_out = d_mapped ? d_mapped + off[r] : nullptr;
+      j.k = (int)k;
+      j.ct = cts + (size_t)r * k;
+      jobs.push_back(j);
+      ids.push_back(r);
+      if (jobs.size() == kRegionMapJobs) flush();
+    }
+    flush();
+    if (d_out) {
+      dq::launch_scatter_coords(d_mapped, d_coords, (uint32_t)n, width, d_out, st);
+      DQ_HIP(hipGetLastError());
+    }
+  }
+  for (void* p : {(void*)d_offsets, (void*)d_colors, (void*)d_coords, (void*)d_mapped})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return rc;
+}
+
+int64_t dq_hip_quant_region_map_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                    uint32_t nregions, const uint32_t* d_pixels, uint32_t k, uint32_t* d_out,
+                                    uint32_t* cts, uint32_t* k_outs, int max_iters, void* stream) {
+  if (!region_map_args_ok(d_regions, width, height, nregions, d_pixels, k, d_out, cts, k_outs, max_iters)) return -1;
+  hipStream_t st = engine_stream(device, stream);
+  return quant_region_map_on(device, st, d_regions, width, height, nregions, d_pixels, k, d_out, cts, k_outs,
+                             max_iters);
+}
+
+int64_t dq_hip_quant_region_map(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                                const uint32_t* pixels, uint32_t k, uint32_t* out, uint32_t* cts, uint32_t* k_outs,
+                                int max_iters) {
+  if (!region_map_args_ok(regions, width, height, nregions, pixels, k, out, cts, k_outs, max_iters)) return -1;
+  const int device = current_device();
+  hipStream_t st = engine_for(device).stream();
+  const size_t n = (size_t)width * height;
+  uint32_t *d_regions = nullptr, *d_pixels = nullptr, *d_out = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
+  if (out) DQ_HIP(hipMallocAsync((void**)&d_out, n * 4, st));
+  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
+  const int64_t rc = quant_region_map_on(device, st, d_regions, width, height, nregions, d_pixels, k, d_out, cts,
+                                         k_outs, max_iters);
+  if (rc >= 0 && out) {
+    DQ_HIP(hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+  }
+  for (void* p : {(void*)d_regions, (void*)d_pixels, (void*)d_out})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return rc;
 }
 
 // Synthetic frames of the benchmark configs (SURVEY 8c/8d generator) and the

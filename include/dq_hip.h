@@ -416,6 +416,83 @@ int64_t dq_hip_segment_labels(const void *labels, int label_bytes, uint32_t widt
                               uint32_t *bbox, uint32_t *first, uint64_t *sums,
                               uint32_t *rounds /*may be NULL*/);
 
+/* ---- pixel lists (region map -> the pixels of every region, on the device) --
+ * The reference keeps a vector<Coord> per region, gathers inPixels[i] =
+ * Vec3BToUID(inputImg(c.y, c.x)) from it before the region's quant_recurse
+ * (ClusteringSegmentation.cpp:1795-1800) and paints outPixels[i] back at
+ * Coord i (:1836-1846).  These entries build all the lists of a region map at
+ * once, in CSR form, and run the per-region calls on them.
+ * Definition.  A stable counting sort of the pixels by region id: ONE exact
+ * integer answer that does not depend on scheduling.  With n = width * height
+ * and every id < nregions = R (not checked, like Coords; the kernels skip a
+ * larger id, whose pixel is then in no list, and write nothing out of bounds):
+ *   d_offsets[r] = the number of pixels whose id is < r, d_offsets[R] = n
+ *   (an id that owns no pixel is allowed: its range is empty);
+ *   the j-th pixel of region r in raster order (increasing p = y * width + x)
+ *   is entry d_offsets[r] + j of each output array given (n words each):
+ *     d_index   p
+ *     d_coords  x | y << 16   (the Coord word dq_hip_gather_bgr24_dev reads)
+ *     d_colors  d_pixels[p], the whole word
+ * d_offsets is required; each of the three arrays may be NULL (all three NULL:
+ * the offsets only); d_colors needs d_pixels.
+ * Accepted maps.  T = the sum, over the ids present, of (last row - first row
+ * + 1).  Every map with T <= n is taken.  A 4- or 8-connected region has a
+ * pixel in every row it spans, so the maps of dq_hip_label_regions_dev and
+ * dq_hip_merge_regions_dev always qualify; other maps do when they fit.
+ * Returns 0, synchronous on return.  -2 when T > n: decided once T is known
+ * and before any output array is written (d_offsets included).  -1, before any
+ * device work, for: NULL d_regions or d_offsets; width or height 0 or above
+ * 65535; n above 2^31 - 1; nregions 0 or above 2^31 - 1; an array not 4-byte
+ * aligned; d_colors without d_pixels.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 8 B per region + 4 B per 1024
+ * regions + 4 B; then, once T is read back (4 bytes), 4 B per table entry (T
+ * <= n entries) + 4 B per 1024 entries + 4 B.
+ * One wave walks one row of the map, 64 pixels at a time: a 65535 x 1 map is
+ * one wave's work, correct and slow. */
+int64_t dq_hip_region_pixels_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                 uint32_t height, uint32_t nregions,
+                                 uint32_t *d_offsets /* nregions + 1 */,
+                                 uint32_t *d_coords, uint32_t *d_index,
+                                 const uint32_t *d_pixels, uint32_t *d_colors, void *stream);
+/* Host pointers, the current device.  A refused map (-2) leaves them as they were. */
+int64_t dq_hip_region_pixels(const uint32_t *regions, uint32_t width, uint32_t height,
+                             uint32_t nregions, uint32_t *offsets, uint32_t *coords,
+                             uint32_t *index, const uint32_t *pixels, uint32_t *colors);
+/* The inverse of a gather by Coords: d_frame[(c >> 16) * width + (c & 0xFFFF)]
+ * = d_values[i] for the n Coord words c = d_coords[i].  Asynchronous on
+ * `stream`; Coords are not range-checked (as in dq_hip_gather_bgr24_dev).
+ * Returns 0; -1 for a NULL or misaligned pointer or width 0. */
+int dq_hip_scatter_coords_dev(int device, const uint32_t *d_values, const uint32_t *d_coords,
+                              uint32_t n, uint32_t width, uint32_t *d_frame, void *stream);
+/* Region map -> painted frame: the pixel lists above (offsets, Coords, colours),
+ * the nregions + 1 offsets read back, ONE dq_hip_quant_weighted_regions_dev
+ * style call in which region r's list is its range of the colours and its K is
+ * k (the jobs go to that path 8192 at a time: it keeps a pinned argument and
+ * result record per job of a call), and, with d_out, the mapped colours
+ * scattered back to their pixels: every pixel of d_out is written.  Region r's
+ * colortable is cts[r * k .. r * k + k_outs[r]), equal to its own
+ * dq_hip_quant_weighted_dev call on its pixels in raster order.  An id without
+ * a pixel is skipped: k_outs[r] = 0, its cts row untouched.  Returns the total
+ * of empty clusters, synchronous on return; -2 as above; -1, before any device
+ * work, for what dq_hip_region_pixels_dev refuses, NULL d_pixels, cts or
+ * k_outs, a misaligned d_out, k == 0 (or above 2^31 - 1) or max_iters < 1.
+ * Device memory of the call: 4 (nregions + 1) + 4 n bytes (12 n with d_out)
+ * and the scratch above.  The quant runs on the device's engine (its lock is
+ * held for that stage alone). */
+int64_t dq_hip_quant_region_map_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                    uint32_t height, uint32_t nregions,
+                                    const uint32_t *d_pixels, uint32_t k,
+                                    uint32_t *d_out /* n words, may be NULL */,
+                                    uint32_t *cts /* host, nregions * k */,
+                                    uint32_t *k_outs /* host, nregions */, int max_iters,
+                                    void *stream);
+/* Host pointers, the current device (one upload, one download). */
+int64_t dq_hip_quant_region_map(const uint32_t *regions, uint32_t width, uint32_t height,
+                                uint32_t nregions, const uint32_t *pixels, uint32_t k,
+                                uint32_t *out /* may be NULL */, uint32_t *cts,
+                                uint32_t *k_outs, int max_iters);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
