@@ -1403,7 +1403,9 @@ void Engine::next_active(FrameState& f, std::vector<int>* active) {
 }
 
 // Final centres (:1029-1094): round, pack, drop empty clusters.
-void Engine::finish_frame(FrameState& f, bool last) {
+// num_points: the clustering's points where they are not the frame's pixels
+// (the weighted path's colour table), 0 otherwise.
+void Engine::finish_frame(FrameState& f, bool last, uint64_t num_points) {
   FrameJob& job = *f.job;
   const int k = job.k;
   int out = 0, empty = 0;
@@ -1415,7 +1417,8 @@ void Engine::finish_frame(FrameState& f, bool last) {
   if (k == 1) {
     // No split happens: mean[0] keeps its zero initialisation (:309).
     job.ct[out++] = 0;
-    if (last) last_sizes[0] = (int64_t)(job.n_global ? job.n_global : job.n);
+    // size[0] = num_points (:329 leaves the one cluster every point)
+    if (last) last_sizes[0] = (int64_t)(num_points ? num_points : (job.n_global ? job.n_global : job.n));
   } else {
     for (int ic = 0; ic < k; ++ic) {
       const Node& nd = nodes_[f.leaf[ic]];
@@ -1993,7 +1996,7 @@ void Engine::run_weighted(FrameJob& job, int max_iters, bool dedup_map, hipStrea
       next_active(f, &active);
     }
   }
-  finish_frame(f, true);
+  finish_frame(f, true, nu);
   if (dedup_map) {
     std::vector<uint32_t> table;
     const int m = dedup_colortable(job.ct, job.k_out, table);

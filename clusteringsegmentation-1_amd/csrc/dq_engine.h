@@ -394,7 +394,7 @@ class Engine {
   uint64_t round_tile_len(uint64_t total) const;
   void replay(FrameState& f);
   void next_active(FrameState& f, std::vector<int>* active);
-  void finish_frame(FrameState& f, bool last);
+  void finish_frame(FrameState& f, bool last, uint64_t num_points = 0);
   const uint8_t* buf_ptr(int buf, const FrameState& f, int shard) const;
   // bytes a pass reads per point of a node: the caller's packed frame (a
   // root) or the planar working buffers

@@ -22,7 +22,7 @@ do not reproduce (its harness details are not recoverable); the fixtures below
 are regenerated from the reference itself by this script and are the pin.
 
 Fixture files (all data, no code): kats.json, cases.json/.npz, c1.npz,
-big.json/.npz, png.json/.npz, map.json, weighted.json, varpart.json/.npz, png/*.png (the two
+big.json/.npz, png.json/.npz, map.json, weighted.json, weighted2/3.json/.npz, varpart.json/.npz, png/*.png (the two
 sample images the reference ships in tests/), and map2.json (--only map2: it needs only
 libdqref.so and rewrites no other fixture).
 """
@@ -291,6 +291,23 @@ def main():
         fx.dump_json("weighted2.json", res)
         np.savez_compressed(os.path.join(HERE, "weighted2.npz"), **arrs)
         print("weighted2: %d cases, %d where UW differs" % (len(res), sum(r["uw_differs"] for r in res)))
+
+    # ---- 8b'. weighted path at the edges of the one-launch kernel's own
+    #        mechanisms (tests/wsmall_edges.py: hash buckets and slots, its four
+    #        limits, fold and partition lengths, map ties): out hash,
+    #        colortable, trace, centroids
+    if want("weighted3"):
+        import wsmall_edges as we
+        res, arrs = [], {}
+        for i, spec in enumerate(we.case_specs()):
+            px = we.build(spec)
+            out, ct, trace, means = full_run(ref, instr, px, spec["k"], 0)
+            res.append(dict(spec=spec, n_px=int(len(px)), **rec(out, ct, trace)))
+            arrs["trace_%d" % i] = trace.astype(np.int32)
+            arrs["means_%d" % i] = means
+        fx.dump_json("weighted3.json", res)
+        np.savez_compressed(os.path.join(HERE, "weighted3.npz"), **arrs)
+        print("weighted3: %d cases" % len(res))
 
     # ---- 8c. quant_varpart_fast's cut_bits / decimation paths (num_bits < 8,
     #        dec_factor > 1): colortable, trace and centroids of the mangled
