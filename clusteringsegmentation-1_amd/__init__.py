@@ -30,6 +30,10 @@ Pixel lists of a region map (stable counting sort by id: offsets, indexes,
 Coords, colours), their inverse and region map -> per-region quant -> frame:
     region_pixels_device, region_pixels, scatter_coords_device,
     quant_region_map_device, quant_region_map
+Capture windows of a region map (per region the pixels of the d x d blocks within
+L1 distance e of its own blocks: one pixel in many lists) and a quant per window:
+    region_windows_device, region_windows,
+    quant_region_windows_device, quant_region_windows
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -117,6 +121,16 @@ def lib():
                                          c.c_int, vp], c.c_int64),
         "dq_hip_quant_region_map": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp, vp, vp, c.c_int],
                                     c.c_int64),
+        "dq_hip_region_windows_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp,
+                                       c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, vp], c.c_int64),
+        "dq_hip_region_windows": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, c.c_uint32,
+                                   vp, c.c_uint32, vp, vp, vp, vp], c.c_int64),
+        "dq_hip_quant_region_windows_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32,
+                                             vp, vp, c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, c.c_uint32, vp, vp,
+                                             vp, c.c_int, vp], c.c_int64),
+        "dq_hip_quant_region_windows": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp,
+                                         c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, c.c_uint32, vp, vp, vp, c.c_int],
+                                        c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -1135,6 +1149,211 @@ def quant_region_map(regions2d, pixels, num_clusters, num_regions=None, max_iter
     r = lib().dq_hip_quant_region_map(_ptr(reg), w, h, nreg, _ptr(px), k, _ptr(out) if paint else None, _ptr(cts),
                                       _ptr(k_outs), max_iters)
     return out, cts, k_outs, _pixels_result(r, "dq_hip_quant_region_map")
+
+
+# ---------------------------------------------------------------------------
+# Capture windows of a region map (include/dq_hip.h, "capture windows"): per
+# region the pixels of the block x block blocks at L1 distance <= expand from a
+# block the region has a pixel in, block by block in raster order, without the
+# masked pixels -- the lists captureRegionMask works on.  One pixel is in many
+# lists: the total length M is not bounded by the map and is counted first.
+WINDOWS_MAX_BLOCK = 8
+WINDOWS_MAX_EXPAND = 3
+WINDOWS_MAX_ENTRIES = (1 << 32) - 2     # M (and the pairs of a block and a member id)
+WINDOWS_BLOCK, WINDOWS_EXPAND = 4, 2    # the reference's
+
+
+class WindowsOverflowError(DivQuantError):
+    """The library's -3: the lists hold 2^32 - 1 entries or more."""
+
+
+class WindowsCapacityError(DivQuantError):
+    """The library's -4: the mapped colours were asked for and the lists are
+    longer than the capacity given (the offsets are written: their last word
+    is the length needed)."""
+
+
+def _windows_scalars(block, expand, min_area, capacity):
+    block, expand = int(block), int(expand)
+    if not 1 <= block <= WINDOWS_MAX_BLOCK:
+        raise ValueError("block %d: 1 .. 8" % block)
+    if not 0 <= expand <= WINDOWS_MAX_EXPAND:
+        raise ValueError("expand %d: 0 .. 3" % expand)
+    return block, expand, _scalar32(min_area, "min_area"), _scalar32(capacity, "capacity")
+
+
+def _windows_result(r, name):
+    if r == -2:
+        raise RegionRowsError("%s: the windows span more block rows in total than they have blocks" % name)
+    if r == -3:
+        raise WindowsOverflowError("%s: the lists hold 2^32 - 1 entries or more" % name)
+    if r == -4:
+        raise WindowsCapacityError("%s: the lists are longer than the capacity given" % name)
+    if r < 0:
+        raise DivQuantError("%s: bad arguments" % name)
+    return int(r)
+
+
+def _windows_tensors(n, nreg, cap, t_regions, t_offsets, t_mask, t_area, t_pixels, lists):
+    """The tensor checks of the windows calls; lists: (tensor, name) of `cap` words each."""
+    _elems(t_regions, n, 4, "t_regions")
+    _elems(t_offsets, nreg + 1, 4, "t_offsets")
+    if t_mask is not None:
+        _elems(t_mask, n, 1, "t_mask")
+    if t_area is not None:
+        _elems(t_area, nreg, 4, "t_area")
+    if t_pixels is not None:
+        _elems(t_pixels, n, 4, "t_pixels")
+    for t, what in lists:
+        if t is not None:
+            _elems(t, cap, 4, what)
+    if cap > 0 and all(t is None for t, _ in lists):
+        raise ValueError("a capacity without a list array")
+
+
+def _opt(t):
+    return _dptr(t) if t is not None else None
+
+
+def region_windows_device(t_regions, width, height, num_regions, t_offsets, block=WINDOWS_BLOCK, expand=WINDOWS_EXPAND,
+                          t_mask=None, t_area=None, min_area=0, capacity=0, t_coords=None, t_index=None,
+                          t_pixels=None, t_colors=None, device=0, stream=None):
+    """The capture windows of a device-resident width x height map of region
+    ids (< num_regions each; contiguous, 4-byte elements).  t_mask: width *
+    height bytes, nonzero = consumed, left out of every list; t_area
+    (num_regions words) with min_area: a region with t_area[r] <= min_area has
+    no window.  t_offsets gets num_regions + 1 words: t_offsets[r] = the length
+    of the lists of the ids < r, the last one M.  Each of t_coords (x | y <<
+    16), t_index (y * width + x) and t_colors (t_pixels there; needs
+    t_pixels), `capacity` words, is filled when given and M <= capacity, and
+    not touched when M > capacity.  Returns M: call without list arrays
+    (capacity 0) for it, then with room.  Synchronous.  ValueError for bad
+    tensors, shapes or scalars (nothing runs), RegionRowsError when the
+    library refuses the map, WindowsOverflowError for M >= 2^32 - 1 (nothing
+    is written)."""
+    width, height, nreg = _pixels_shape(width, height, num_regions)
+    block, expand, min_area, cap = _windows_scalars(block, expand, min_area, capacity)
+    _windows_tensors(width * height, nreg, cap, t_regions, t_offsets, t_mask, t_area, t_pixels,
+                     ((t_coords, "t_coords"), (t_index, "t_index"), (t_colors, "t_colors")))
+    if t_colors is not None and t_pixels is None:
+        raise ValueError("t_colors without t_pixels")
+    r = lib().dq_hip_region_windows_dev(device, _dptr(t_regions), width, height, nreg, block, expand, _opt(t_mask),
+                                        _opt(t_area), min_area, _dptr(t_offsets), cap, _opt(t_coords), _opt(t_index),
+                                        _opt(t_pixels), _opt(t_colors), _stream_ptr(stream))
+    return _windows_result(r, "dq_hip_region_windows_dev")
+
+
+def _windows_host(regions2d, num_regions, block, expand, mask, area, min_area, pixels):
+    """The host inputs of a windows call, checked: (reg, nreg, block, expand, mask, area, min_area, px)."""
+    reg, nreg = _region_map(regions2d, num_regions)
+    block, expand, min_area, _ = _windows_scalars(block, expand, min_area, 0)
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.size != reg.size or mask.dtype.itemsize != 1:
+            raise ValueError("mask: one byte per pixel")
+        mask = np.ascontiguousarray(mask).view(np.uint8).reshape(-1)
+    if area is not None:
+        area = _u32(area).reshape(-1)
+        if area.size < nreg:
+            raise ValueError("%d areas for %d regions" % (area.size, nreg))
+    px = None
+    if pixels is not None:
+        px = _u32(pixels).reshape(-1)
+        if px.size != reg.size:
+            raise ValueError("%d pixels for %d region ids" % (px.size, reg.size))
+    return reg, nreg, block, expand, mask, area, min_area, px
+
+
+def _optp(a):
+    return _ptr(a) if a is not None else None
+
+
+def region_windows(regions2d, num_regions=None, block=WINDOWS_BLOCK, expand=WINDOWS_EXPAND, mask=None, area=None,
+                   min_area=0, pixels=None):
+    """The capture windows of a host (H, W) map of region ids (integers of at
+    most 4 bytes; num_regions=None takes regions2d.max() + 1); mask (H * W
+    bytes), area with min_area and pixels (H * W words) as in
+    region_windows_device.  Two calls: the count, then the lists with room.
+    Returns (offsets, index, coords, colours), uint32: offsets (num_regions +
+    1,), and per list entry the pixel's index y * W + x, its Coord word
+    x | y << 16 and, with pixels, its frame word (None without)."""
+    reg, nreg, block, expand, mask, area, min_area, px = _windows_host(regions2d, num_regions, block, expand, mask,
+                                                                       area, min_area, pixels)
+    h, w = reg.shape
+    _require_gpu()
+    offsets = np.zeros(nreg + 1, np.uint32)
+
+    def call(cap, coords, index, colours):
+        r = lib().dq_hip_region_windows(_ptr(reg), w, h, nreg, block, expand, _optp(mask), _optp(area), min_area,
+                                        _ptr(offsets), cap, _optp(coords), _optp(index),
+                                        _optp(px) if colours is not None else None, _optp(colours))
+        return _windows_result(r, "dq_hip_region_windows")
+    total = call(0, None, None, None)
+    index, coords = np.zeros(total, np.uint32), np.zeros(total, np.uint32)
+    colours = np.zeros(total, np.uint32) if px is not None else None
+    if total:
+        call(total, coords, index, colours)
+    return offsets, index, coords, colours
+
+
+def quant_region_windows_device(t_regions, width, height, num_regions, t_pixels, num_clusters, t_offsets,
+                                block=WINDOWS_BLOCK, expand=WINDOWS_EXPAND, t_mask=None, t_area=None, min_area=0,
+                                capacity=0, t_out=None, t_coords=None, t_index=None, t_colors=None, max_iters=10,
+                                cts=None, k_outs=None, device=0, stream=None):
+    """quant_recurse(N_window, .., K, allPixelsUnique=0) of every capture
+    window of a device-resident region map: region_windows_device with the same
+    arguments, then one call of the weighted-regions path in which region r's
+    input is its window's colours in list order.  t_out (`capacity` words)
+    gets the mapped colours in list order (windows overlap: there is no frame
+    to paint).  Returns (cts, k_outs, empty): region r's colortable is
+    cts[r, :k_outs[r]]; an empty window has k_outs[r] == 0 and its row of cts
+    (zeros, or the array passed in) untouched.  The reference quantises a
+    heuristic subset of the window (combinedCoords): that subset is not built
+    here.  Synchronous.  ValueError for bad tensors, shapes or scalars (nothing
+    runs); RegionRowsError, WindowsOverflowError as region_windows_device;
+    WindowsCapacityError when t_out is given and the lists are longer than
+    capacity (t_offsets is written, nothing is quantised)."""
+    width, height, nreg = _pixels_shape(width, height, num_regions)
+    block, expand, min_area, cap = _windows_scalars(block, expand, min_area, capacity)
+    k, max_iters = _region_map_scalars(num_clusters, max_iters)
+    if t_pixels is None:
+        raise ValueError("the frame is needed")
+    _windows_tensors(width * height, nreg, cap, t_regions, t_offsets, t_mask, t_area, t_pixels,
+                     ((t_coords, "t_coords"), (t_index, "t_index"), (t_colors, "t_colors"), (t_out, "t_out")))
+    cts, k_outs = _region_map_tables(nreg, k, cts, k_outs)
+    r = lib().dq_hip_quant_region_windows_dev(device, _dptr(t_regions), width, height, nreg, block, expand,
+                                              _opt(t_mask), _opt(t_area), min_area, _dptr(t_offsets), cap,
+                                              _opt(t_coords), _opt(t_index), _dptr(t_pixels), _opt(t_colors), k,
+                                              _opt(t_out), _ptr(cts), _ptr(k_outs), max_iters, _stream_ptr(stream))
+    return cts, k_outs, _windows_result(r, "dq_hip_quant_region_windows_dev")
+
+
+def quant_region_windows(regions2d, pixels, num_clusters, num_regions=None, block=WINDOWS_BLOCK,
+                         expand=WINDOWS_EXPAND, mask=None, area=None, min_area=0, max_iters=10, mapped=True, cts=None,
+                         k_outs=None):
+    """quant_region_windows_device on a host (H, W) map of region ids and its
+    frame (H * W packed 0x00RRGGBB words).  Returns (offsets, out, cts, k_outs,
+    empty): out holds the mapped colours in list order (None with
+    mapped=False, which also saves the counting call)."""
+    if pixels is None:
+        raise ValueError("the frame is needed")
+    reg, nreg, block, expand, mask, area, min_area, px = _windows_host(regions2d, num_regions, block, expand, mask,
+                                                                       area, min_area, pixels)
+    h, w = reg.shape
+    k, max_iters = _region_map_scalars(num_clusters, max_iters)
+    cts, k_outs = _region_map_tables(nreg, k, cts, k_outs)
+    _require_gpu()
+    offsets = np.zeros(nreg + 1, np.uint32)
+    total, out = 0, None
+    if mapped:
+        r = lib().dq_hip_region_windows(_ptr(reg), w, h, nreg, block, expand, _optp(mask), _optp(area), min_area,
+                                        _ptr(offsets), 0, None, None, None, None)
+        total = _windows_result(r, "dq_hip_region_windows")
+        out = np.zeros(total, np.uint32)
+    r = lib().dq_hip_quant_region_windows(_ptr(reg), w, h, nreg, block, expand, _optp(mask), _optp(area), min_area,
+                                          _ptr(offsets), total, None, None, _ptr(px), None, k,
+                                          _ptr(out) if total else None, _ptr(cts), _ptr(k_outs), max_iters)
+    return offsets, out, cts, k_outs, _windows_result(r, "dq_hip_quant_region_windows")
 
 
 # ---------------------------------------------------------------------------

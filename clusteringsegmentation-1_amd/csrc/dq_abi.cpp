@@ -28,6 +28,7 @@
 #include "dq_pixels.h"
 #include "dq_regions.h"
 #include "dq_weighted.h"
+#include "dq_windows.h"
 
 #include <rccl/rccl.h>
 #include <map>
@@ -1312,6 +1313,51 @@ static bool region_map_args_ok(const uint32_t* regions, uint32_t width, uint32_t
   return pixels_args_ok(regions, width, height, nregions, regions, nullptr, nullptr, pixels, nullptr);
 }
 
+// One weighted-regions call over the ranges [off[r], off[r + 1]) of d_colors, region r's K = k: its
+// colortable to cts + r * k, its count to k_outs[r] (0 for an empty range, the row untouched), its
+// mapped colours to the same range of d_mapped when given.  Returns the total of empty clusters.
+static int64_t quant_ranges_on(int device, hipStream_t st, const std::vector<uint32_t>& off, uint32_t nregions,
+                               const uint32_t* d_colors, uint32_t* d_mapped, uint32_t k, uint32_t* cts,
+                               uint32_t* k_outs, int max_iters) {
+  int64_t empty = 0;
+  Engine& e = engine_for(device);
+  std::vector<dq::FrameJob> jobs;
+  std::vector<uint32_t> ids;
+  jobs.reserve(std::min<size_t>(nregions, kRegionMapJobs));
+  ids.reserve(jobs.capacity());
+  auto flush = [&] {
+    if (jobs.empty()) return;
+    {
+      std::lock_guard<std::mutex> g(e.mutex());
+      e.run_weighted_regions(jobs.data(), (int)jobs.size(), max_iters, st);
+    }
+    for (size_t i = 0; i < jobs.size(); ++i) {
+      k_outs[ids[i]] = (uint32_t)jobs[i].k_out;
+      empty += jobs[i].num_empty;
+    }
+    jobs.clear();
+    ids.clear();
+  };
+  for (uint32_t r = 0; r < nregions; ++r) {
+    const uint32_t len = off[r + 1] - off[r];
+    if (len == 0) {   // an empty list: no call, its colortable row stays as it is
+      k_outs[r] = 0;
+      continue;
+    }
+    dq::FrameJob j;
+    j.d_in = d_colors + off[r];
+    j.n = len;
+    j.d_out = d_mapped ? d_mapped + off[r] : nullptr;
+    j.k = (int)k;
+    j.ct = cts + (size_t)r * k;
+    jobs.push_back(j);
+    ids.push_back(r);
+    if (jobs.size() == kRegionMapJobs) flush();
+  }
+  flush();
+  return empty;
+}
+
 static int64_t quant_region_map_on(int device, hipStream_t st, const uint32_t* d_regions, uint32_t width,
                                    uint32_t height, uint32_t nregions, const uint32_t* d_pixels, uint32_t k,
                                    uint32_t* d_out, uint32_t* cts, uint32_t* k_outs, int max_iters) {
@@ -1330,41 +1376,7 @@ static int64_t quant_region_map_on(int device, hipStream_t st, const uint32_t* d
     std::vector<uint32_t> off(no);
     DQ_HIP(hipMemcpyAsync(off.data(), d_offsets, no * 4, hipMemcpyDeviceToHost, st));
     DQ_HIP(hipStreamSynchronize(st));
-    Engine& e = engine_for(device);
-    std::vector<dq::FrameJob> jobs;
-    std::vector<uint32_t> ids;
-    jobs.reserve(std::min<size_t>(nregions, kRegionMapJobs));
-    ids.reserve(jobs.capacity());
-    auto flush = [&] {
-      if (jobs.empty()) return;
-      {
-        std::lock_guard<std::mutex> g(e.mutex());
-        e.run_weighted_regions(jobs.data(), (int)jobs.size(), max_iters, st);
-      }
-      for (size_t i = 0; i < jobs.size(); ++i) {
-        k_outs[ids[i]] = (uint32_t)jobs[i].k_out;
-        rc += jobs[i].num_empty;
-      }
-      jobs.clear();
-      ids.clear();
-    };
-    for (uint32_t r = 0; r < nregions; ++r) {
-      const uint32_t len = off[r + 1] - off[r];
-      if (len == 0) {   // an id without a pixel: no call, its colortable row stays as it is
-        k_outs[r] = 0;
-        continue;
-      }
-      dq::FrameJob j;
-      j.d_in = d_colors + off[r];
-      j.n = len;
-      j.d_out = d_mapped ? d_mapped + off[r] : nullptr;
-      j.k = (int)k;
-      j.ct = cts + (size_t)r * k;
-      jobs.push_back(j);
-      ids.push_back(r);
-      if (jobs.size() == kRegionMapJobs) flush();
-    }
-    flush();
+    rc = quant_ranges_on(device, st, off, nregions, d_colors, d_mapped, k, cts, k_outs, max_iters);
     if (d_out) {
       dq::launch_scatter_coords(d_mapped, d_coords, (uint32_t)n, width, d_out, st);
       DQ_HIP(hipGetLastError());
@@ -1405,6 +1417,243 @@ int64_t dq_hip_quant_region_map(const uint32_t* regions, uint32_t width, uint32_
     DQ_HIP(hipStreamSynchronize(st));
   }
   for (void* p : {(void*)d_regions, (void*)d_pixels, (void*)d_out})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return rc;
+}
+
+// Capture windows of a region map (dq_windows.hip).  Every argument check comes
+// before the first HIP call.
+static bool windows_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, uint32_t block,
+                            uint32_t expand, const uint32_t* area, const uint32_t* offsets, uint32_t cap,
+                            const uint32_t* coords, const uint32_t* index, const uint32_t* pixels,
+                            const uint32_t* colors) {
+  if (!pixels_args_ok(regions, width, height, nregions, offsets, coords, index, pixels, colors)) return false;
+  if (block < 1 || block > 8 || expand > 3) return false;
+  if (((uintptr_t)area & 3u) != 0) return false;
+  if (cap > 0 && !coords && !index && !colors) return false;
+  return true;
+}
+
+// Enqueues the parts on st with scratch owned by the call and waits.  Two small
+// read-backs sit between them: P and T size the pairs and the table (a map with
+// T > P is refused there), and M decides -3 and whether the lists fit, before
+// any output array is written.
+static int64_t region_windows_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                 uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
+                                 const uint32_t* d_area, uint32_t min_area, uint32_t* d_offsets, uint32_t cap,
+                                 uint32_t* d_coords, uint32_t* d_index, const uint32_t* d_pixels, uint32_t* d_colors) {
+  dq::WindowsArgs a{d_regions, width,    height,  nregions, block,    expand,   d_mask, d_area,
+                    min_area,  d_offsets, d_coords, d_index, d_pixels, d_colors, nullptr, nullptr};
+  DQ_HIP(hipMallocAsync((void**)&a.blocks, dq::windows_blocks_bytes(width, height, block, nregions), st));
+  dq::launch_windows_blocks(a, st);
+  DQ_HIP(hipGetLastError());
+  uint32_t npairs = 0, nrows = 0, total = 0;
+  DQ_HIP(hipMemcpyAsync(&npairs, dq::windows_pairs_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipMemcpyAsync(&nrows, dq::windows_rows_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  int64_t rc;
+  if (npairs == 0xFFFFFFFFu) {
+    rc = -3;   // (the pairs are indexed by words)
+  } else if (nrows > npairs) {
+    rc = -2;
+  } else {
+    DQ_HIP(hipMallocAsync((void**)&a.pairs, dq::windows_pairs_bytes(npairs, nrows), st));
+    if (npairs != 0 && nrows != 0) {
+      dq::launch_windows_count(a, npairs, nrows, st);
+      DQ_HIP(hipGetLastError());
+      DQ_HIP(hipMemcpyAsync(&total, dq::windows_total_word(a, npairs, nrows), 4, hipMemcpyDeviceToHost, st));
+      DQ_HIP(hipStreamSynchronize(st));
+    }
+    if (total == 0xFFFFFFFFu) {
+      rc = -3;
+    } else {
+      rc = total;
+      dq::launch_windows_offsets(a, npairs, nrows, total, st);
+      if (total <= cap) dq::launch_windows_lists(a, npairs, nrows, total, st);
+      DQ_HIP(hipGetLastError());
+    }
+    DQ_HIP(hipFreeAsync(a.pairs, st));
+  }
+  DQ_HIP(hipFreeAsync(a.blocks, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return rc;
+}
+
+int64_t dq_hip_region_windows_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                  uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
+                                  const uint32_t* d_area, uint32_t min_area, uint32_t* d_offsets, uint32_t cap,
+                                  uint32_t* d_coords, uint32_t* d_index, const uint32_t* d_pixels, uint32_t* d_colors,
+                                  void* stream) {
+  if (!windows_args_ok(d_regions, width, height, nregions, block, expand, d_area, d_offsets, cap, d_coords, d_index,
+                       d_pixels, d_colors))
+    return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  return region_windows_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area, d_offsets,
+                           cap, d_coords, d_index, d_pixels, d_colors);
+}
+
+// The device copies of a host windows call's inputs.
+struct WindowsInputs {
+  uint32_t *regions = nullptr, *area = nullptr, *pixels = nullptr;
+  uint8_t* mask = nullptr;
+  void upload(hipStream_t st, size_t n, uint32_t nregions, const uint32_t* h_regions, const uint8_t* h_mask,
+              const uint32_t* h_area, const uint32_t* h_pixels) {
+    DQ_HIP(hipMallocAsync((void**)&regions, n * 4, st));
+    DQ_HIP(hipMemcpyAsync(regions, h_regions, n * 4, hipMemcpyHostToDevice, st));
+    if (h_mask) {
+      DQ_HIP(hipMallocAsync((void**)&mask, n, st));
+      DQ_HIP(hipMemcpyAsync(mask, h_mask, n, hipMemcpyHostToDevice, st));
+    }
+    if (h_area) {
+      DQ_HIP(hipMallocAsync((void**)&area, (size_t)nregions * 4, st));
+      DQ_HIP(hipMemcpyAsync(area, h_area, (size_t)nregions * 4, hipMemcpyHostToDevice, st));
+    }
+    if (h_pixels) {
+      DQ_HIP(hipMallocAsync((void**)&pixels, n * 4, st));
+      DQ_HIP(hipMemcpyAsync(pixels, h_pixels, n * 4, hipMemcpyHostToDevice, st));
+    }
+  }
+  void release(hipStream_t st) {
+    for (void* p : {(void*)regions, (void*)area, (void*)pixels, (void*)mask})
+      if (p) DQ_HIP(hipFreeAsync(p, st));
+  }
+};
+
+int64_t dq_hip_region_windows(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                              uint32_t block, uint32_t expand, const uint8_t* mask, const uint32_t* area,
+                              uint32_t min_area, uint32_t* offsets, uint32_t cap, uint32_t* coords, uint32_t* index,
+                              const uint32_t* pixels, uint32_t* colors) {
+  if (!windows_args_ok(regions, width, height, nregions, block, expand, area, offsets, cap, coords, index, pixels,
+                       colors))
+    return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
+  WindowsInputs in;
+  in.upload(st, n, nregions, regions, mask, area, colors ? pixels : nullptr);
+  uint32_t *d_offsets = nullptr, *d_coords = nullptr, *d_index = nullptr, *d_colors = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
+  if (cap && coords) DQ_HIP(hipMallocAsync((void**)&d_coords, (size_t)cap * 4, st));
+  if (cap && index) DQ_HIP(hipMallocAsync((void**)&d_index, (size_t)cap * 4, st));
+  if (cap && colors) DQ_HIP(hipMallocAsync((void**)&d_colors, (size_t)cap * 4, st));
+  const int64_t rc = region_windows_on(st, in.regions, width, height, nregions, block, expand, in.mask, in.area,
+                                       min_area, d_offsets, cap, d_coords, d_index, in.pixels, d_colors);
+  if (rc >= 0) {   // (a refused map leaves the host arrays as they were)
+    DQ_HIP(hipMemcpyAsync(offsets, d_offsets, no * 4, hipMemcpyDeviceToHost, st));
+    if (rc > 0 && rc <= (int64_t)cap) {
+      if (d_coords) DQ_HIP(hipMemcpyAsync(coords, d_coords, (size_t)rc * 4, hipMemcpyDeviceToHost, st));
+      if (d_index) DQ_HIP(hipMemcpyAsync(index, d_index, (size_t)rc * 4, hipMemcpyDeviceToHost, st));
+      if (d_colors) DQ_HIP(hipMemcpyAsync(colors, d_colors, (size_t)rc * 4, hipMemcpyDeviceToHost, st));
+    }
+    DQ_HIP(hipStreamSynchronize(st));
+  }
+  in.release(st);
+  for (void* p : {(void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_colors})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return rc;
+}
+
+// Region map -> capture windows -> one weighted quant per window.
+static bool quant_windows_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                                  uint32_t block, uint32_t expand, const uint32_t* area, const uint32_t* offsets,
+                                  uint32_t cap, const uint32_t* coords, const uint32_t* index, const uint32_t* pixels,
+                                  const uint32_t* colors, uint32_t k, const uint32_t* out, const uint32_t* cts,
+                                  const uint32_t* k_outs, int max_iters) {
+  if (!pixels || !cts || !k_outs || k == 0 || k > 0x7FFFFFFFu || max_iters < 1) return false;
+  if (((uintptr_t)out & 3u) != 0) return false;
+  if (cap > 0 && !coords && !index && !colors && out) coords = out;   // (d_out alone is a list array of cap words)
+  return windows_args_ok(regions, width, height, nregions, block, expand, area, offsets, cap, coords, index, pixels,
+                         colors);
+}
+
+static int64_t quant_region_windows_on(int device, hipStream_t st, const uint32_t* d_regions, uint32_t width,
+                                       uint32_t height, uint32_t nregions, uint32_t block, uint32_t expand,
+                                       const uint8_t* d_mask, const uint32_t* d_area, uint32_t min_area,
+                                       uint32_t* d_offsets, uint32_t cap, uint32_t* d_coords, uint32_t* d_index,
+                                       const uint32_t* d_pixels, uint32_t* d_colors, uint32_t k, uint32_t* d_out,
+                                       uint32_t* cts, uint32_t* k_outs, int max_iters) {
+  const size_t no = (size_t)nregions + 1;
+  const bool lists = d_coords || d_index || d_colors;
+  int64_t rc = region_windows_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area,
+                                 d_offsets, lists ? cap : 0u, d_coords, d_index, d_pixels, d_colors);
+  if (rc < 0) return rc;
+  const int64_t total = rc;
+  if (d_out && total > (int64_t)cap) return -4;
+  // the colours in list order: the caller's when they were written, else the call's own
+  uint32_t *own_offsets = nullptr, *own_colors = nullptr;
+  const uint32_t* colors = d_colors;
+  if (!(d_colors && total <= (int64_t)cap) && total > 0) {
+    DQ_HIP(hipMallocAsync((void**)&own_offsets, no * 4, st));
+    DQ_HIP(hipMallocAsync((void**)&own_colors, (size_t)total * 4, st));
+    rc = region_windows_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area,
+                           own_offsets, (uint32_t)total, nullptr, nullptr, d_pixels, own_colors);
+    colors = own_colors;
+  }
+  if (rc >= 0) {
+    std::vector<uint32_t> off(no);
+    DQ_HIP(hipMemcpyAsync(off.data(), d_offsets, no * 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+    rc = quant_ranges_on(device, st, off, nregions, colors, d_out, k, cts, k_outs, max_iters);
+  }
+  for (void* p : {(void*)own_offsets, (void*)own_colors})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return rc;
+}
+
+int64_t dq_hip_quant_region_windows_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                        uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
+                                        const uint32_t* d_area, uint32_t min_area, uint32_t* d_offsets, uint32_t cap,
+                                        uint32_t* d_coords, uint32_t* d_index, const uint32_t* d_pixels,
+                                        uint32_t* d_colors, uint32_t k, uint32_t* d_out, uint32_t* cts,
+                                        uint32_t* k_outs, int max_iters, void* stream) {
+  if (!quant_windows_args_ok(d_regions, width, height, nregions, block, expand, d_area, d_offsets, cap, d_coords,
+                             d_index, d_pixels, d_colors, k, d_out, cts, k_outs, max_iters))
+    return -1;
+  hipStream_t st = engine_stream(device, stream);
+  return quant_region_windows_on(device, st, d_regions, width, height, nregions, block, expand, d_mask, d_area,
+                                 min_area, d_offsets, cap, d_coords, d_index, d_pixels, d_colors, k, d_out, cts, k_outs,
+                                 max_iters);
+}
+
+int64_t dq_hip_quant_region_windows(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                                    uint32_t block, uint32_t expand, const uint8_t* mask, const uint32_t* area,
+                                    uint32_t min_area, uint32_t* offsets, uint32_t cap, uint32_t* coords,
+                                    uint32_t* index, const uint32_t* pixels, uint32_t* colors, uint32_t k,
+                                    uint32_t* out, uint32_t* cts, uint32_t* k_outs, int max_iters) {
+  if (!quant_windows_args_ok(regions, width, height, nregions, block, expand, area, offsets, cap, coords, index,
+                             pixels, colors, k, out, cts, k_outs, max_iters))
+    return -1;
+  const int device = current_device();
+  hipStream_t st = engine_for(device).stream();
+  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
+  WindowsInputs in;
+  in.upload(st, n, nregions, regions, mask, area, pixels);
+  uint32_t *d_offsets = nullptr, *d_coords = nullptr, *d_index = nullptr, *d_colors = nullptr, *d_out = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
+  if (cap && coords) DQ_HIP(hipMallocAsync((void**)&d_coords, (size_t)cap * 4, st));
+  if (cap && index) DQ_HIP(hipMallocAsync((void**)&d_index, (size_t)cap * 4, st));
+  if (cap && colors) DQ_HIP(hipMallocAsync((void**)&d_colors, (size_t)cap * 4, st));
+  if (out) DQ_HIP(hipMallocAsync((void**)&d_out, (size_t)std::max<uint32_t>(cap, 1u) * 4, st));
+  uint32_t total = 0;
+  const int64_t rc = quant_region_windows_on(device, st, in.regions, width, height, nregions, block, expand, in.mask,
+                                             in.area, min_area, d_offsets, cap, d_coords, d_index, in.pixels, d_colors,
+                                             k, d_out, cts, k_outs, max_iters);
+  if (rc >= 0) {   // (a refused call leaves the host arrays as they were)
+    DQ_HIP(hipMemcpyAsync(offsets, d_offsets, no * 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipMemcpyAsync(&total, d_offsets + nregions, 4, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+    if (total > 0 && total <= cap) {
+      if (d_coords) DQ_HIP(hipMemcpyAsync(coords, d_coords, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+      if (d_index) DQ_HIP(hipMemcpyAsync(index, d_index, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+      if (d_colors) DQ_HIP(hipMemcpyAsync(colors, d_colors, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+      if (d_out) DQ_HIP(hipMemcpyAsync(out, d_out, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+      DQ_HIP(hipStreamSynchronize(st));
+    }
+  }
+  in.release(st);
+  for (void* p : {(void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_colors, (void*)d_out})
     if (p) DQ_HIP(hipFreeAsync(p, st));
   return rc;
 }

@@ -21,7 +21,7 @@
 //             in a wave whose pixel above (below) has another id, gathered
 //             per workgroup in 128 LDS slots first
 //   2 scan    heights y1 - y0 + 1 (0: id absent) -> rowbase[] and T, three
-//             kernels (sums per 1024, one workgroup over the sums, apply);
+//             kernels (dq_scan.h: sums per 1024, one workgroup over the sums, apply);
 //             the sums saturate at 2^32 - 1, so T > n is seen however large T is
 //             (the host reads T back and allocates the table)
 //   3 count   table[rowbase[r] + y - y0[r]] += run length, one add per run
@@ -47,12 +47,13 @@
 
 #include "dq_pixels.h"
 #include "dq_regions.h"
+#include "dq_scan.h"
 
 namespace dq {
 namespace {
 
-constexpr uint32_t kChunk = kRegionChunk;
-constexpr int kThreads = 256;
+constexpr uint32_t kChunk = scan::kChunk;
+constexpr int kThreads = scan::kThreads;
 static_assert(kChunk == 4 * kThreads, "four rounds of one pixel per thread in the flat passes");
 constexpr uint32_t kRowsPerBlock = kThreads / 64;   // the walk: one wave per row
 constexpr uint32_t kRowSlots = 128;                 // the rows pass: LDS slots per workgroup
@@ -63,92 +64,16 @@ constexpr uint32_t kNoId = 0xFFFFFFFFu;    // R <= 2^31 - 1: never a valid id
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;   // y0 of an id without a pixel
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;  // T <= n <= 2^31 - 1: never a table entry
 
-__device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) {
-  const uint32_t s = a + b;
-  return s < a ? 0xFFFFFFFFu : s;
-}
+using scan::chunks_of;
 
-// Exclusive prefix sum of v over the workgroup's threads (NW waves) and the
-// workgroup's total, both saturating (min(sum, 2^32 - 1) is associative).
-// Every thread of the workgroup calls it.
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(inc, d);
-    if (lane >= d) inc = sat_add(inc, t);
+// the scan over the regions: element i is y1[i] - y0[i] + 1 (0 when y0[i] is kNoRow) with y1 = v
+struct Heights {
+  const uint32_t *y0, *v;
+  __device__ uint32_t operator()(uint32_t i) const {
+    const uint32_t a = y0[i];
+    return a == kNoRow ? 0u : v[i] - a + 1u;
   }
-  uint32_t excl = __shfl_up(inc, 1);
-  if (lane == 0) excl = 0;
-  __syncthreads();   // (wsum may still be read from the previous call)
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-    const uint32_t s = wsum[w];
-    if (w < wave) off = sat_add(off, s);
-    tot = sat_add(tot, s);
-  }
-  total = tot;
-  return sat_add(off, excl);
-}
-
-// ---- the scan: v[0 .. n) -> its exclusive prefix sums, in place ----------------
-// HEIGHTS: element i is y1[i] - y0[i] + 1 (0 when y0[i] is kNoRow) with y1 = v.
-template <bool HEIGHTS>
-__device__ __forceinline__ uint32_t scan_value(const uint32_t* y0, const uint32_t* v, uint32_t i, uint32_t n) {
-  if (i >= n) return 0u;
-  if (!HEIGHTS) return v[i];
-  const uint32_t a = y0[i];
-  return a == kNoRow ? 0u : v[i] - a + 1u;
-}
-
-template <bool HEIGHTS>
-__global__ __launch_bounds__(kThreads) void pixels_scan_sums_kernel(const uint32_t* y0, const uint32_t* v, uint32_t n,
-                                                                   uint32_t* __restrict__ sums) {
-  __shared__ uint32_t wsum[kThreads / 64];
-  uint32_t c = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < kChunk / kThreads; ++k)
-    c = sat_add(c, scan_value<HEIGHTS>(y0, v, blockIdx.x * kChunk + k * kThreads + threadIdx.x, n));
-  uint32_t total;
-  block_excl_scan<kThreads / 64>(c, wsum, total);
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// sums[0 .. nchunks) -> their exclusive prefix sums, sums[nchunks] = the total.
-__global__ __launch_bounds__(1024) void pixels_scan_top_kernel(uint32_t* sums, uint32_t nchunks) {
-  __shared__ uint32_t wsum[16];
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < nchunks; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < nchunks ? sums[i] : 0u;
-    uint32_t total;
-    const uint32_t excl = block_excl_scan<16>(v, wsum, total);
-    if (i < nchunks) sums[i] = sat_add(carry, excl);
-    carry = sat_add(carry, total);
-  }
-  if (threadIdx.x == 0) sums[nchunks] = carry;
-}
-
-template <bool HEIGHTS>
-__global__ __launch_bounds__(kThreads) void pixels_scan_apply_kernel(const uint32_t* y0, uint32_t* v, uint32_t n,
-                                                                    const uint32_t* __restrict__ sums) {
-  __shared__ uint32_t wsum[kThreads / 64];
-  uint32_t carry = sums[blockIdx.x];
-#pragma unroll 1
-  for (uint32_t k = 0; k < kChunk / kThreads; ++k) {
-    const uint32_t i = blockIdx.x * kChunk + k * kThreads + threadIdx.x;
-    const uint32_t val = scan_value<HEIGHTS>(y0, v, i, n);   // (read by the thread that then writes v[i])
-    uint32_t total;
-    const uint32_t excl = block_excl_scan<kThreads / 64>(val, wsum, total);
-    if (i < n) v[i] = sat_add(carry, excl);
-    carry = sat_add(carry, total);
-  }
-}
+};
 
 // ---- 1 rows ------------------------------------------------------------------
 // A pixel whose upper neighbour has its id is not in the id's first row; of the
@@ -320,17 +245,6 @@ __global__ __launch_bounds__(kThreads) void scatter_coords_kernel(const uint32_t
   frame[(size_t)(c >> 16) * W + (c & 0xFFFFu)] = values[i];
 }
 
-uint32_t chunks_of(uint32_t n) { return (n + kChunk - 1) / kChunk; }
-
-// v[0 .. n) -> exclusive prefix sums in place; sums: chunks_of(n) + 1 words, the last one the total.
-template <bool HEIGHTS>
-void launch_scan(const uint32_t* y0, uint32_t* v, uint32_t n, uint32_t* sums, hipStream_t st) {
-  const uint32_t nchunks = chunks_of(n);
-  pixels_scan_sums_kernel<HEIGHTS><<<nchunks, kThreads, 0, st>>>(y0, v, n, sums);
-  pixels_scan_top_kernel<<<1, 1024, 0, st>>>(sums, nchunks);
-  pixels_scan_apply_kernel<HEIGHTS><<<nchunks, kThreads, 0, st>>>(y0, v, n, sums);
-}
-
 }  // namespace
 
 // y0 | y1, then rowbase | the sums of the scan over the regions
@@ -352,7 +266,7 @@ void launch_pixels_rows(const PixelsArgs& a, hipStream_t st) {
   (void)hipMemsetAsync(y0, 0xFF, (size_t)R * 4, st);
   (void)hipMemsetAsync(y1, 0, (size_t)R * 4, st);
   pixels_rows_kernel<<<chunks_of(n), kThreads, 0, st>>>(a.regions, n, W, H, R, y0, y1);
-  launch_scan<true>(y0, y1, R, sums, st);   // y1 is rowbase from here on
+  scan::launch(Heights{y0, y1}, y1, R, sums, st);   // y1 is rowbase from here on
 }
 
 void launch_pixels_lists(const PixelsArgs& a, uint32_t T, hipStream_t st) {
@@ -362,7 +276,7 @@ void launch_pixels_lists(const PixelsArgs& a, uint32_t T, hipStream_t st) {
   if (T != 0) {
     (void)hipMemsetAsync(table, 0, (size_t)T * 4, st);
     pixels_count_kernel<<<chunks_of(n), kThreads, 0, st>>>(a.regions, n, W, R, T, y0, rowbase, table);
-    launch_scan<false>(nullptr, table, T, table + T, st);
+    scan::launch(scan::Words{table}, table, T, table + T, st);
   }
   pixels_offsets_kernel<<<R / kThreads + 1, kThreads, 0, st>>>(R, T, n, rowbase, table, a.offsets);
   if (T != 0 && (a.index || a.coords || a.colors))

@@ -493,6 +493,102 @@ int64_t dq_hip_quant_region_map(const uint32_t *regions, uint32_t width, uint32_
                                 uint32_t *out /* may be NULL */, uint32_t *cts,
                                 uint32_t *k_outs, int max_iters);
 
+/* ---- capture windows of a region map ----------------------------------------
+ * The block-dilated pixel lists the reference's captureRegionMask works on
+ * (ClusteringSegmentation.cpp:1038-1190 through morphRegionMask, :849-1029, and
+ * expandBlockRegion, OpenCVUtil.cpp:668-731; DESIGN.md 5a''''''): one list per
+ * region, and one pixel in many lists.
+ * The grid: BW = ceil(width / block) by BH = ceil(height / block) blocks, pixel
+ * (x, y) in block (x / block, y / block).  own(r) = the blocks that hold a
+ * pixel of r (the mask plays no part).  window(r) = the blocks of the grid at
+ * L1 distance <= expand from a block of own(r): `expand` dilations by OpenCV's
+ * 3 x 3 MORPH_ELLIPSE element, which is the plus-shaped cross, with nothing
+ * coming in from outside the grid.  The reference has block 4, expand 2.
+ * With d_area (nregions words) a region with d_area[r] <= min_area is absent
+ * (:1061-1069): its window is empty; its pixels stay pixels of the frame.
+ * The list of r: the blocks of window(r) in raster order of blocks, in each
+ * block its pixels in raster order, without the pixels outside the frame
+ * (right and bottom blocks are clipped) and the pixels p with d_mask[p] != 0
+ * (n bytes, may be NULL; consumed by an earlier capture, :1079-1105).
+ * d_offsets[r] = the total length of the lists of the ids < r, d_offsets[nregions]
+ * = M; entry d_offsets[r] + j of d_index, d_coords and d_colors is the j-th
+ * pixel of the list of r: p, x | y << 16 and d_pixels[p], the words of
+ * dq_hip_region_pixels_dev.  With block 1, expand 0, no mask and no area these
+ * are exactly the pixel lists.  An id >= nregions (not allowed) founds no
+ * block and has no list; its pixels are pixels of the frame like any other.
+ * Returns M >= 0, synchronous on return; d_offsets is then written.  The three
+ * list arrays, `cap` words each and each may be NULL, are written when M <= cap
+ * and not touched when M > cap: call with cap 0 and no list array for M, then
+ * with room.  -3 when M, or P below, reaches 2^32 - 1: the sums saturate there
+ * (so an M of exactly 2^32 - 1 is given up too); decided before any output
+ * array is written.  -2 for a map the call refuses, before any output array is
+ * written: with P = the sum over the regions of |window(r)| and T = the sum
+ * over the regions with a window of the block rows it spans, a map with T > P.
+ * A 4- or 8-connected region has a window block in every block row its window
+ * spans (its own blocks cover the rows of the region, the blocks straight
+ * above and below them the `expand` rows on each side), so the maps of
+ * dq_hip_label_regions_dev and dq_hip_merge_regions_dev always qualify; other
+ * maps do when they fit.  -1, before any device work, for: NULL d_regions or
+ * d_offsets; width or height 0 or above 65535; n above 2^31 - 1; nregions 0 or
+ * above 2^31 - 1; block outside 1..8; expand above 3; a word array not 4-byte
+ * aligned; d_colors without d_pixels; cap > 0 with all three list arrays NULL.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap), with NB = BW * BH blocks:
+ * 4 (block^2 + 2) B per block + 8 B per region + 4 B per 1024 of each + 12 B;
+ * then, once P and T are read back (8 bytes), 8 B per pair + 4 B per table
+ * entry (T <= P) + 4 B per 1024 entries + 4 B.  M is read back as well.
+ * One wave walks the pairs of one block row, 64 at a time. */
+int64_t dq_hip_region_windows_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                  uint32_t height, uint32_t nregions, uint32_t block,
+                                  uint32_t expand, const uint8_t *d_mask, const uint32_t *d_area,
+                                  uint32_t min_area, uint32_t *d_offsets /* nregions + 1 */,
+                                  uint32_t cap, uint32_t *d_coords, uint32_t *d_index,
+                                  const uint32_t *d_pixels, uint32_t *d_colors, void *stream);
+/* Host pointers, the current device.  A call that returns < 0 leaves them as
+ * they were; M > cap leaves the list arrays as they were. */
+int64_t dq_hip_region_windows(const uint32_t *regions, uint32_t width, uint32_t height,
+                              uint32_t nregions, uint32_t block, uint32_t expand,
+                              const uint8_t *mask, const uint32_t *area, uint32_t min_area,
+                              uint32_t *offsets, uint32_t cap, uint32_t *coords, uint32_t *index,
+                              const uint32_t *pixels, uint32_t *colors);
+/* Region map -> one colortable per capture window: the windows call above with
+ * the same arguments (d_pixels is needed), the nregions + 1 offsets read back,
+ * and ONE dq_hip_quant_weighted_regions_dev style call in which region r's
+ * input is its range of the colours in list order and its K is k (marshalled
+ * as in dq_hip_quant_region_map_dev).  cts[r * k .. r * k + k_outs[r]) equals
+ * the region's own dq_hip_quant_weighted_dev call on its window in list order;
+ * an empty window gives k_outs[r] = 0 and leaves its cts row untouched.  d_out
+ * (`cap` words, may be NULL) gets the mapped colours in list order: windows
+ * overlap, so there is no scatter to a frame.  The colours are the caller's
+ * d_colors when M <= cap, else the call's own (the windows are then built a
+ * second time, with room).  Returns the total of empty clusters, synchronous on
+ * return; -4 when M > cap with d_out given (d_offsets is written, nothing is
+ * quantised); -2 and -3 as above; -1, before any device work, for what the
+ * windows call refuses (d_out counts as a list array there), NULL d_pixels,
+ * cts or k_outs, a misaligned d_out, k == 0 (or above 2^31 - 1) or max_iters
+ * < 1.  The reference quantises a heuristic subset of the window
+ * (combinedCoords, :1791-1803); that subset stays out of scope: this entry
+ * gives the per-window table that the subset's logic starts from. */
+int64_t dq_hip_quant_region_windows_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                        uint32_t height, uint32_t nregions, uint32_t block,
+                                        uint32_t expand, const uint8_t *d_mask,
+                                        const uint32_t *d_area, uint32_t min_area,
+                                        uint32_t *d_offsets /* nregions + 1 */, uint32_t cap,
+                                        uint32_t *d_coords, uint32_t *d_index,
+                                        const uint32_t *d_pixels, uint32_t *d_colors, uint32_t k,
+                                        uint32_t *d_out /* cap words, may be NULL */,
+                                        uint32_t *cts /* host, nregions * k */,
+                                        uint32_t *k_outs /* host, nregions */, int max_iters,
+                                        void *stream);
+/* Host pointers, the current device. */
+int64_t dq_hip_quant_region_windows(const uint32_t *regions, uint32_t width, uint32_t height,
+                                    uint32_t nregions, uint32_t block, uint32_t expand,
+                                    const uint8_t *mask, const uint32_t *area, uint32_t min_area,
+                                    uint32_t *offsets, uint32_t cap, uint32_t *coords,
+                                    uint32_t *index, const uint32_t *pixels, uint32_t *colors,
+                                    uint32_t k, uint32_t *out /* cap words, may be NULL */,
+                                    uint32_t *cts, uint32_t *k_outs, int max_iters);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
