@@ -131,6 +131,12 @@ def lib():
         "dq_hip_quant_region_windows": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp,
                                          c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, c.c_uint32, vp, vp, vp, c.c_int],
                                         c.c_int64),
+        "dq_hip_window_tags_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp,
+                                    c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp], c.c_int64),
+        "dq_hip_window_tags": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, c.c_uint32, vp,
+                                c.c_uint32, vp, vp, vp, vp, vp, vp, vp], c.c_int64),
+        "dq_hip_window_votes_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, vp, vp, c.c_uint32, vp, vp, vp, c.c_uint32,
+                                     vp, vp, vp], c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -1354,6 +1360,123 @@ def quant_region_windows(regions2d, pixels, num_clusters, num_regions=None, bloc
                                           _ptr(offsets), total, None, None, _ptr(px), None, k,
                                           _ptr(out) if total else None, _ptr(cts), _ptr(k_outs), max_iters)
     return offsets, out, cts, k_outs, _windows_result(r, "dq_hip_quant_region_windows")
+
+
+# ---------------------------------------------------------------------------
+# Window tags (include/dq_hip.h, "window tags"): per capture window which
+# regions' pixels lie in it and how many each, in the order the ids first
+# appear in the window's list; and per window and side (the region's own
+# pixels, everything else) how many entries were mapped to each colortable
+# entry.  Exact integers, independent of scheduling.
+WINDOW_NO_ID = 0xFFFFFFFF               # best other / best vote: there is none
+WINDOW_VOTES_MAX_CLUSTERS = 256
+
+
+def _window_tags_result(r, name):
+    if r == -3:   # (the call cannot say which of its three counts it was)
+        raise WindowsOverflowError("%s: the lists hold 2^32 - 1 entries or more, or the windows as many pairs "
+                                   "(block, member id), or the call as many contributions (pair, id alive in the "
+                                   "block)" % name)
+    return _windows_result(r, name)
+
+
+def window_tags_device(t_regions, width, height, num_regions, t_rows, block=WINDOWS_BLOCK, expand=WINDOWS_EXPAND,
+                       t_mask=None, t_area=None, min_area=0, capacity=0, t_ids=None, t_counts=None, t_first=None,
+                       t_inside=None, t_best=None, t_best_count=None, t_offsets=None, device=0, stream=None):
+    """The tag histogram of every capture window of a device-resident region
+    map; t_regions .. min_area as in region_windows_device.  With c(r, s) = the
+    entries of the list of r whose pixel has id s and f(r, s) = the first of
+    them: t_rows gets num_regions + 1 CSR offsets, the last one E; entry
+    t_rows[r] + i of t_ids, t_counts and t_first (`capacity` words each) is the
+    i-th id s of row r, c(r, s) and f(r, s), in ascending f: filled when given
+    and E <= capacity, not touched when E > capacity.  t_inside, t_best and
+    t_best_count (num_regions words each) get c(r, r), the other id with the
+    largest count (ties to the lowest id; WINDOW_NO_ID without one) and that
+    count; t_offsets (num_regions + 1) the windows call's offsets.  Returns E:
+    call without entry arrays (capacity 0) for it, then with room.
+    Synchronous.  ValueError for bad tensors, shapes or scalars (nothing runs),
+    RegionRowsError when the library refuses the map, WindowsOverflowError for
+    2^32 - 1 list entries or contributions or more (nothing is written)."""
+    width, height, nreg = _pixels_shape(width, height, num_regions)
+    block, expand, min_area, cap = _windows_scalars(block, expand, min_area, capacity)
+    _windows_tensors(width * height, nreg, cap, t_regions, t_rows, t_mask, t_area, None,
+                     ((t_ids, "t_ids"), (t_counts, "t_counts"), (t_first, "t_first")))
+    for t, what in ((t_inside, "t_inside"), (t_best, "t_best"), (t_best_count, "t_best_count")):
+        if t is not None:
+            _elems(t, nreg, 4, what)
+    if t_offsets is not None:
+        _elems(t_offsets, nreg + 1, 4, "t_offsets")
+    r = lib().dq_hip_window_tags_dev(device, _dptr(t_regions), width, height, nreg, block, expand, _opt(t_mask),
+                                     _opt(t_area), min_area, _dptr(t_rows), cap, _opt(t_ids), _opt(t_counts),
+                                     _opt(t_first), _opt(t_inside), _opt(t_best), _opt(t_best_count), _opt(t_offsets),
+                                     _stream_ptr(stream))
+    return _window_tags_result(r, "dq_hip_window_tags_dev")
+
+
+def window_tags(regions2d, num_regions=None, block=WINDOWS_BLOCK, expand=WINDOWS_EXPAND, mask=None, area=None,
+                min_area=0):
+    """window_tags_device on a host (H, W) map of region ids (as
+    region_windows).  Two calls: the count, then the entries with room.
+    Returns a dict of uint32 arrays: rows and offsets (num_regions + 1,), ids,
+    counts and first (E,), inside, best and best_count (num_regions,)."""
+    reg, nreg, block, expand, mask, area, min_area, _ = _windows_host(regions2d, num_regions, block, expand, mask,
+                                                                      area, min_area, None)
+    h, w = reg.shape
+    _require_gpu()
+    out = {k: np.zeros(nreg + 1, np.uint32) for k in ("rows", "offsets")}
+    out.update({k: np.zeros(nreg, np.uint32) for k in ("inside", "best", "best_count")})
+
+    def call(cap):
+        r = lib().dq_hip_window_tags(_ptr(reg), w, h, nreg, block, expand, _optp(mask), _optp(area), min_area,
+                                     _ptr(out["rows"]), cap, _optp(out.get("ids")), _optp(out.get("counts")),
+                                     _optp(out.get("first")), _ptr(out["inside"]), _ptr(out["best"]),
+                                     _ptr(out["best_count"]), _ptr(out["offsets"]))
+        return _window_tags_result(r, "dq_hip_window_tags")
+    entries = call(0)
+    out.update({k: np.zeros(entries, np.uint32) for k in ("ids", "counts", "first")})
+    if entries:
+        call(entries)
+    return out
+
+
+def window_votes_device(t_regions, num_pixels, num_regions, t_offsets, t_index, total, t_mapped, cts, k_outs,
+                        num_clusters, t_votes, t_best, device=0, stream=None):
+    """The inside / outside votes of every window's quant: t_offsets, t_index
+    and total as region_windows_device gave them, t_mapped (total words) the
+    t_out of quant_region_windows_device, cts (num_regions, num_clusters) and
+    k_outs (num_regions) the host arrays it returned.  For entry j of the list
+    of r, mapped to the lowest entry i < k_outs[r] of r's colortable with its
+    colour (low 24 bits): t_votes[(2 r + side) * num_clusters + i] += 1, side 0
+    for a pixel of r itself and 1 for any other.  t_votes: num_regions * 2 *
+    num_clusters words, all written; t_best: num_regions * 2 words, per side the
+    lowest i with the largest non-zero count or WINDOW_NO_ID.  Returns the
+    entries whose colour is not in their colortable (0 on the pipeline's own
+    outputs).  Synchronous.  ValueError for bad tensors or scalars."""
+    n, nreg, total, k = int(num_pixels), int(num_regions), int(total), int(num_clusters)
+    if not 1 <= n <= PIXELS_MAX_PIXELS:
+        raise ValueError("num_pixels %d: 1 .. 2^31 - 1" % n)
+    if not 1 <= nreg <= PIXELS_MAX_REGIONS:
+        raise ValueError("num_regions %d: 1 .. 2^31 - 1" % nreg)
+    if not 0 <= total <= WINDOWS_MAX_ENTRIES:
+        raise ValueError("total %d: 0 .. 2^32 - 2" % total)
+    if not 1 <= k <= WINDOW_VOTES_MAX_CLUSTERS:
+        raise ValueError("num_clusters %d: 1 .. 256" % k)
+    _elems(t_regions, n, 4, "t_regions")
+    _elems(t_offsets, nreg + 1, 4, "t_offsets")
+    for t, what in ((t_index, "t_index"), (t_mapped, "t_mapped")):
+        if t is not None or total > 0:
+            _elems(t, total, 4, what)
+    _elems(t_votes, nreg * 2 * k, 4, "t_votes")
+    _elems(t_best, nreg * 2, 4, "t_best")
+    if cts is None or k_outs is None:
+        raise ValueError("cts and k_outs are needed")
+    cts, k_outs = _region_map_tables(nreg, k, cts, k_outs)
+    r = lib().dq_hip_window_votes_dev(device, _dptr(t_regions), n, nreg, _dptr(t_offsets), _opt(t_index), total,
+                                      _opt(t_mapped), _ptr(cts), _ptr(k_outs), k, _dptr(t_votes), _dptr(t_best),
+                                      _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_window_votes_dev: bad arguments")
+    return int(r)
 
 
 # ---------------------------------------------------------------------------

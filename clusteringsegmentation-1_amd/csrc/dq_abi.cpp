@@ -29,6 +29,7 @@
 #include "dq_regions.h"
 #include "dq_weighted.h"
 #include "dq_windows.h"
+#include "dq_wtags.h"
 
 #include <rccl/rccl.h>
 #include <map>
@@ -1656,6 +1657,186 @@ int64_t dq_hip_quant_region_windows(const uint32_t* regions, uint32_t width, uin
   for (void* p : {(void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_colors, (void*)d_out})
     if (p) DQ_HIP(hipFreeAsync(p, st));
   return rc;
+}
+
+// Window tags (dq_wtags.hip): the windows stage up to the pair positions, then
+// the tag histogram of every window from its pairs.  Every argument check comes
+// before the first HIP call.
+static bool wtags_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, uint32_t block,
+                          uint32_t expand, const uint32_t* area, const uint32_t* rows, uint32_t cap,
+                          const uint32_t* ids, const uint32_t* counts, const uint32_t* first, const uint32_t* inside,
+                          const uint32_t* best, const uint32_t* best_count, const uint32_t* offsets) {
+  // (rows stands where the windows call has its offsets: required; the entry arrays are its list arrays)
+  if (!windows_args_ok(regions, width, height, nregions, block, expand, area, rows, 0, ids, counts, nullptr, nullptr))
+    return false;
+  if (cap > 0 && !ids && !counts && !first) return false;
+  for (const void* p : {(const void*)first, (const void*)inside, (const void*)best, (const void*)best_count,
+                        (const void*)offsets})
+    if (((uintptr_t)p & 3u) != 0) return false;
+  return true;
+}
+
+// Three read-backs with a synchronisation each: P, T and Q (Q sizes the table;
+// a map with T > P is refused and -3 is decided there), M (-3; sizes the bitmap)
+// and E (do the entries fit), all before any output array is written.
+static int64_t window_tags_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                              uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
+                              const uint32_t* d_area, uint32_t min_area, uint32_t* d_rows, uint32_t cap,
+                              uint32_t* d_ids, uint32_t* d_counts, uint32_t* d_first, uint32_t* d_inside,
+                              uint32_t* d_best, uint32_t* d_best_count, uint32_t* d_offsets) {
+  const size_t no = (size_t)nregions + 1;
+  uint32_t *own_offsets = nullptr, *pair_ids = nullptr;
+  dq::WindowsArgs a{d_regions, width,   height,  nregions, block,   expand,  d_mask,  d_area,
+                    min_area,  nullptr, nullptr, nullptr,  nullptr, nullptr, nullptr, nullptr};
+  DQ_HIP(hipMallocAsync((void**)&a.blocks, dq::windows_blocks_bytes(width, height, block, nregions), st));
+  dq::WindowsView v = dq::windows_view(a, 0);   // (what the first part leaves: the pairs come later)
+  dq::WtagsArgs t{};
+  t.regions = d_regions, t.width = width, t.height = height, t.nregions = nregions, t.block = block;
+  t.mask = d_mask, t.nblocks = v.nblocks, t.pairbase = v.pairbase;
+  t.rows = d_rows, t.ids = d_ids, t.counts = d_counts, t.first = d_first;
+  t.inside = d_inside, t.best = d_best, t.best_count = d_best_count;
+  DQ_HIP(hipMallocAsync((void**)&t.live, dq::wtags_live_bytes(v.nblocks), st));
+  dq::launch_windows_blocks(a, st);
+  dq::launch_wtags_count(t, st);   // (the members of every block are counted by then: Q needs no pair)
+  DQ_HIP(hipGetLastError());
+  uint32_t npairs = 0, nrows = 0, total = 0, ncontribs = 0, nentries = 0;
+  DQ_HIP(hipMemcpyAsync(&npairs, dq::windows_pairs_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipMemcpyAsync(&nrows, dq::windows_rows_word(a), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipMemcpyAsync(&ncontribs, dq::wtags_contribs_word(t), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  int64_t rc;
+  if (npairs == 0xFFFFFFFFu || ncontribs == 0xFFFFFFFFu) {
+    rc = -3;
+  } else if (nrows > npairs) {
+    rc = -2;
+  } else {
+    DQ_HIP(hipMallocAsync((void**)&a.pairs, dq::windows_pairs_bytes(npairs, nrows), st));
+    if (npairs != 0 && nrows != 0) {
+      dq::launch_windows_count(a, npairs, nrows, st);
+      DQ_HIP(hipGetLastError());
+      DQ_HIP(hipMemcpyAsync(&total, dq::windows_total_word(a, npairs, nrows), 4, hipMemcpyDeviceToHost, st));
+      DQ_HIP(hipStreamSynchronize(st));
+    } else {
+      ncontribs = 0;   // (no pair, no contribution)
+    }
+    if (total == 0xFFFFFFFFu) {
+      rc = -3;
+    } else {
+      v = dq::windows_view(a, npairs);
+      if (ncontribs != 0) {
+        // the member ids of the pairs: the walk below turns the windows stage's into positions
+        DQ_HIP(hipMallocAsync((void**)&pair_ids, (size_t)npairs * 4, st));
+        DQ_HIP(hipMemcpyAsync(pair_ids, v.pair_word, (size_t)npairs * 4, hipMemcpyDeviceToDevice, st));
+      }
+      t.pair_id = pair_ids, t.pair_pos = v.pair_word, t.npairs = npairs, t.total = total;
+      a.offsets = d_offsets;
+      if (!a.offsets) {
+        DQ_HIP(hipMallocAsync((void**)&own_offsets, no * 4, st));
+        a.offsets = own_offsets;
+      }
+      t.offsets = a.offsets;
+      dq::launch_windows_offsets(a, npairs, nrows, total, st);
+      if (ncontribs != 0) dq::launch_windows_walk(a, npairs, nrows, st);
+      DQ_HIP(hipMallocAsync((void**)&t.table, dq::wtags_table_bytes(ncontribs, total, nregions), st));
+      dq::launch_wtags_fill(t, ncontribs, st);
+      DQ_HIP(hipGetLastError());
+      DQ_HIP(hipMemcpyAsync(&nentries, dq::wtags_entries_word(t, ncontribs), 4, hipMemcpyDeviceToHost, st));
+      DQ_HIP(hipStreamSynchronize(st));
+      rc = nentries;
+      dq::launch_wtags_rows(t, ncontribs, st);
+      if (nentries <= cap) dq::launch_wtags_entries(t, ncontribs, nentries, st);
+      DQ_HIP(hipGetLastError());
+      DQ_HIP(hipFreeAsync(t.table, st));
+    }
+    for (void* p : {(void*)pair_ids, (void*)own_offsets, (void*)a.pairs})
+      if (p) DQ_HIP(hipFreeAsync(p, st));
+  }
+  DQ_HIP(hipFreeAsync(t.live, st));
+  DQ_HIP(hipFreeAsync(a.blocks, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return rc;
+}
+
+int64_t dq_hip_window_tags_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                               uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
+                               const uint32_t* d_area, uint32_t min_area, uint32_t* d_rows, uint32_t cap,
+                               uint32_t* d_ids, uint32_t* d_counts, uint32_t* d_first, uint32_t* d_inside,
+                               uint32_t* d_best, uint32_t* d_best_count, uint32_t* d_offsets, void* stream) {
+  if (!wtags_args_ok(d_regions, width, height, nregions, block, expand, d_area, d_rows, cap, d_ids, d_counts, d_first,
+                     d_inside, d_best, d_best_count, d_offsets))
+    return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  return window_tags_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area, d_rows, cap,
+                        d_ids, d_counts, d_first, d_inside, d_best, d_best_count, d_offsets);
+}
+
+int64_t dq_hip_window_tags(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, uint32_t block,
+                           uint32_t expand, const uint8_t* mask, const uint32_t* area, uint32_t min_area,
+                           uint32_t* rows, uint32_t cap, uint32_t* ids, uint32_t* counts, uint32_t* first,
+                           uint32_t* inside, uint32_t* best, uint32_t* best_count, uint32_t* offsets) {
+  if (!wtags_args_ok(regions, width, height, nregions, block, expand, area, rows, cap, ids, counts, first, inside, best,
+                     best_count, offsets))
+    return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
+  WindowsInputs in;
+  in.upload(st, n, nregions, regions, mask, area, nullptr);
+  // the device twins of the host arrays given: rows | offsets, the three entry arrays, the three per region
+  uint32_t* const host[8] = {rows, offsets, ids, counts, first, inside, best, best_count};
+  const size_t words[8] = {no, no, cap, cap, cap, nregions, nregions, nregions};
+  uint32_t* dev[8] = {};
+  for (int i = 0; i < 8; ++i)
+    if (host[i] && words[i]) DQ_HIP(hipMallocAsync((void**)&dev[i], words[i] * 4, st));
+  const int64_t rc = window_tags_on(st, in.regions, width, height, nregions, block, expand, in.mask, in.area, min_area,
+                                    dev[0], cap, dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[1]);
+  if (rc >= 0) {   // (a refused map leaves the host arrays as they were)
+    for (int i = 0; i < 8; ++i) {
+      const bool entries = i >= 2 && i <= 4;
+      if (!dev[i] || (entries && (rc == 0 || rc > (int64_t)cap))) continue;
+      DQ_HIP(hipMemcpyAsync(host[i], dev[i], (entries ? (size_t)rc : words[i]) * 4, hipMemcpyDeviceToHost, st));
+    }
+    DQ_HIP(hipStreamSynchronize(st));
+  }
+  in.release(st);
+  for (uint32_t* p : dev)
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return rc;
+}
+
+// Window votes (dq_wtags.hip).  There is no host-pointer twin: the call consumes
+// device arrays that only the device pipeline produces.
+int64_t dq_hip_window_votes_dev(int device, const uint32_t* d_regions, uint32_t n, uint32_t nregions,
+                                const uint32_t* d_offsets, const uint32_t* d_index, uint32_t total,
+                                const uint32_t* d_mapped, const uint32_t* cts, const uint32_t* k_outs, uint32_t k,
+                                uint32_t* d_votes, uint32_t* d_best, void* stream) {
+  if (!d_regions || !d_offsets || !cts || !k_outs || !d_votes || !d_best) return -1;
+  if (total > 0 && (!d_index || !d_mapped)) return -1;
+  if (n == 0 || n > 0x7FFFFFFFu || nregions == 0 || nregions > 0x7FFFFFFFu || k < 1 || k > dq::kVotesMaxK) return -1;
+  if (total == 0xFFFFFFFFu) return -1;   // (the windows call gives such an M up)
+  for (const void* p : {(const void*)d_regions, (const void*)d_offsets, (const void*)d_index, (const void*)d_mapped,
+                        (const void*)cts, (const void*)k_outs, (const void*)d_votes, (const void*)d_best})
+    if (((uintptr_t)p & 3u) != 0) return -1;
+  hipStream_t st = engine_stream(device, stream);
+  const size_t table = (size_t)nregions * k;
+  uint32_t *d_cts = nullptr, *d_kouts = nullptr;
+  dq::WvotesArgs a{d_regions, n, nregions, d_offsets, d_index, d_mapped, total, k, nullptr, nullptr, nullptr, d_votes,
+                   d_best};
+  DQ_HIP(hipMallocAsync((void**)&d_cts, table * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_kouts, (size_t)nregions * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&a.jobs, dq::wvotes_jobs_bytes(nregions), st));
+  DQ_HIP(hipMemcpyAsync(d_cts, cts, table * 4, hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemcpyAsync(d_kouts, k_outs, (size_t)nregions * 4, hipMemcpyHostToDevice, st));
+  a.cts = d_cts, a.k_outs = d_kouts;
+  dq::launch_wvotes(a, st);
+  DQ_HIP(hipGetLastError());
+  unsigned long long misses = 0;
+  DQ_HIP(hipMemcpyAsync(&misses, dq::wvotes_misses_word(a), 8, hipMemcpyDeviceToHost, st));
+  for (void* p : {(void*)d_cts, (void*)d_kouts, (void*)a.jobs})
+    DQ_HIP(hipFreeAsync(p, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return (int64_t)misses;
 }
 
 // Synthetic frames of the benchmark configs (SURVEY 8c/8d generator) and the

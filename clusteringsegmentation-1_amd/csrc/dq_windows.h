@@ -52,4 +52,17 @@ const uint32_t* windows_total_word(const WindowsArgs& a, uint32_t npairs, uint32
 void launch_windows_offsets(const WindowsArgs& a, uint32_t npairs, uint32_t nrows, uint32_t total, hipStream_t stream);
 void launch_windows_lists(const WindowsArgs& a, uint32_t npairs, uint32_t nrows, uint32_t total, hipStream_t stream);
 
+// For the stages that work on the pairs themselves (dq_wtags.hip): what the parts above leave in
+// the call's scratch.  info[b] = m(b) | distinct ids << 16 and ids[b * block^2 ..] after
+// launch_windows_blocks; pairbase[b] (nblocks + 1 entries) = the first pair of block b;
+// pair_block[i] after launch_windows_count; pair_word[i] = the pair's id after
+// launch_windows_count and its list position after launch_windows_walk.
+struct WindowsView {
+  const uint32_t *info, *ids, *pairbase, *pair_word, *pair_block;
+  uint32_t nblocks;
+};
+WindowsView windows_view(const WindowsArgs& a, uint32_t npairs);
+// The first half of launch_windows_lists alone (after launch_windows_offsets; once per call).
+void launch_windows_walk(const WindowsArgs& a, uint32_t npairs, uint32_t nrows, hipStream_t stream);
+
 }  // namespace dq

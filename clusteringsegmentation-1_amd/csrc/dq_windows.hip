@@ -484,8 +484,14 @@ void launch_windows_offsets(const WindowsArgs& a, uint32_t P, uint32_t T, uint32
                                                                a.pairs + (size_t)P * 2, a.offsets);
 }
 
-void launch_windows_lists(const WindowsArgs& a, uint32_t P, uint32_t T, uint32_t M, hipStream_t st) {
-  if (P == 0 || T == 0 || M == 0 || !(a.index || a.coords || a.colors)) return;
+WindowsView windows_view(const WindowsArgs& a, uint32_t P) {
+  const Grid g = grid_of(a);
+  const BlocksLayout l = blocks_layout(g, a.nregions);
+  return WindowsView{a.blocks + l.info, a.blocks + l.ids, a.blocks + l.counts, a.pairs, a.pairs + P, g.NB};
+}
+
+void launch_windows_walk(const WindowsArgs& a, uint32_t P, uint32_t T, hipStream_t st) {
+  if (P == 0 || T == 0) return;
   const Grid g = grid_of(a);
   const BlocksLayout l = blocks_layout(g, a.nregions);
   uint32_t *pair_id = a.pairs, *pair_block = pair_id + P, *table = pair_block + P;
@@ -493,6 +499,14 @@ void launch_windows_lists(const WindowsArgs& a, uint32_t P, uint32_t T, uint32_t
                                                                         pair_id,
                                                                         pair_block, a.blocks + l.info, a.blocks + l.y0,
                                                                         a.blocks + l.y1, table);
+}
+
+void launch_windows_lists(const WindowsArgs& a, uint32_t P, uint32_t T, uint32_t M, hipStream_t st) {
+  if (P == 0 || T == 0 || M == 0 || !(a.index || a.coords || a.colors)) return;
+  const Grid g = grid_of(a);
+  const BlocksLayout l = blocks_layout(g, a.nregions);
+  uint32_t* pair_id = a.pairs;
+  launch_windows_walk(a, P, T, st);
   windows_fill_kernel<<<(g.NB + kWaves - 1) / kWaves, kThreads, 0, st>>>(g, P, M, a.mask, a.blocks + l.counts, pair_id,
                                                                         a.pixels, a.index, a.coords, a.colors);
 }

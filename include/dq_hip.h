@@ -589,6 +589,101 @@ int64_t dq_hip_quant_region_windows(const uint32_t *regions, uint32_t width, uin
                                     uint32_t k, uint32_t *out /* cap words, may be NULL */,
                                     uint32_t *cts, uint32_t *k_outs, int max_iters);
 
+/* ---- window tags (which regions lie in a window, which colours on which side)
+ * The two exact integer tables the reference reads off every capture window
+ * before its heuristics branch: the tag histogram (tagHistogram,
+ * sort_keys_by_count, mostCommonOtherTag; ClusteringSegmentation.cpp:1644-1663)
+ * and the inside / outside histograms of the window's quant (:2009-2068);
+ * DESIGN.md 5a'''''''.  All terms and the arguments d_regions .. min_area are
+ * those of "capture windows" above.
+ * For a region r with a window and an id s < nregions: c(r, s) = the number of
+ * entries j of the list of r with d_regions[index[j]] == s, f(r, s) = the
+ * smallest such j, relative to the start of r's list.  Row r holds the ids s
+ * with c(r, s) > 0 in ascending f(r, s): the order in which the ids first
+ * appear in the list of r, fixed by the definition alone.  So s = r is an entry
+ * of its own row (the "inside" count); a region the area rule makes absent has
+ * no row and still appears as s in other rows; an id whose pixels in the window
+ * are all masked appears in no row.  Pixels with an id >= nregions (not
+ * allowed) are counted in no entry.  The reference orders a row by count with
+ * undefined ties (unordered_map order through an unstable sort) and uses only
+ * the head of that order, so the call does not sort and gives the head exactly:
+ * best other = the s != r with the largest c(r, s), ties to the lowest id.
+ * Outputs, device word arrays, 4-byte aligned:
+ *   d_rows[nregions + 1]  (required) CSR offsets, d_rows[nregions] = E, the
+ *                         number of entries.  Returns E >= 0, synchronous.
+ *   d_ids, d_counts, d_first  `cap` words each, each may be NULL: entry
+ *                         d_rows[r] + i is the i-th entry of row r: s, c(r, s),
+ *                         f(r, s).  Written when E <= cap, not touched when
+ *                         E > cap; cap 0 with no entry array returns E alone.
+ *   d_inside, d_best, d_best_count  nregions words each, each may be NULL:
+ *                         c(r, r), the best other id (0xFFFFFFFF when the row
+ *                         has no other id) and its count (0 then); a region
+ *                         without a window gets 0, 0xFFFFFFFF, 0.  Written
+ *                         whenever the call returns >= 0, whatever cap.
+ *   d_offsets[nregions + 1]  (may be NULL here) the windows call's offsets.
+ * -1, before any device work, for everything dq_hip_region_windows_dev refuses
+ * (d_rows in the place of its d_offsets), a NULL d_rows, and cap > 0 with all
+ * three entry arrays NULL.  -2 and -3 as the windows call (T > P; P or M
+ * saturated); -3 also when the call's own contribution count Q reaches
+ * 2^32 - 1, Q = the sum over the pairs (block b, member id r) of the windows
+ * stage of the distinct ids with a surviving pixel in b.  All decided before
+ * any output array is written.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): the windows call's (its lists
+ * are never built); 4 B per block + 4 B per 1024 blocks + 4 B; 4 B per pair
+ * (the member ids); then, with Q (read back with P and T), 16 B per slot of a hash
+ * table of the entries, slots = 2 Q (>= 1024, below 2^32); 8 B per 32
+ * list entries (one bit per list position and the rank of every word of them)
+ * + 4 B per 32768 + 24 B; 12 B per region; 4 (nregions + 1) B when d_offsets
+ * is NULL.  E is read back as well.  The table is sized from Q with no upper
+ * bound: like every allocation of the library, one that fails aborts the
+ * process with a message (a map of single-pixel regions without the area rule
+ * can ask for tens of GB). */
+int64_t dq_hip_window_tags_dev(int device, const uint32_t *d_regions, uint32_t width,
+                               uint32_t height, uint32_t nregions, uint32_t block,
+                               uint32_t expand, const uint8_t *d_mask, const uint32_t *d_area,
+                               uint32_t min_area, uint32_t *d_rows /* nregions + 1 */,
+                               uint32_t cap, uint32_t *d_ids, uint32_t *d_counts,
+                               uint32_t *d_first, uint32_t *d_inside, uint32_t *d_best,
+                               uint32_t *d_best_count, uint32_t *d_offsets /* may be NULL */,
+                               void *stream);
+/* Host pointers, the current device.  A call that returns < 0 leaves them as
+ * they were; E > cap leaves the entry arrays as they were. */
+int64_t dq_hip_window_tags(const uint32_t *regions, uint32_t width, uint32_t height,
+                           uint32_t nregions, uint32_t block, uint32_t expand,
+                           const uint8_t *mask, const uint32_t *area, uint32_t min_area,
+                           uint32_t *rows, uint32_t cap, uint32_t *ids, uint32_t *counts,
+                           uint32_t *first, uint32_t *inside, uint32_t *best,
+                           uint32_t *best_count, uint32_t *offsets);
+/* The inside / outside votes of every window's quant.  d_regions: n region
+ * ids; d_offsets (nregions + 1), d_index and total (= M): the windows call's;
+ * d_mapped: M words, the d_out of dq_hip_quant_region_windows_dev; cts
+ * (nregions * k) and k_outs (nregions): HOST arrays as that call returns them,
+ * uploaded by this call in stream order; 1 <= k <= 256 (the reference asserts
+ * <= 256, :1962).  For j in the list of r: side = 0 if
+ * d_regions[d_index[j]] == r, else 1; i = the lowest i < k_outs[r] with
+ * ((cts[r * k + i] ^ d_mapped[j]) & 0xFFFFFF) == 0;
+ * d_votes[(2 r + side) * k + i] += 1.  An entry with no such i (or with a
+ * d_index[j] >= n) is a miss and is counted in no bin.  d_votes: nregions * 2
+ * * k words, all written, zeros included.  d_best: nregions * 2 words, per
+ * side the lowest i with the largest non-zero count (insideQuantPixel /
+ * outsideQuantPixel are cts[r * k + that]), 0xFFFFFFFF when the side has no
+ * vote.  Returns the number of misses (0 on the pipeline's own outputs),
+ * synchronous on return.  -1, before any device work, for a NULL or misaligned
+ * array (d_index and d_mapped may be NULL when total is 0), k outside 1..256,
+ * nregions 0 or above 2^31 - 1, n 0 or above 2^31 - 1, total 2^32 - 1.
+ * Scratch, in stream order, no engine state: the device copies of cts and
+ * k_outs, 4 B per region + 4 B per 1024 regions + 24 B.  A list is cut into
+ * jobs of 2048 entries, one wave each.  There is no host-pointer twin: the
+ * call consumes device arrays that only the device pipeline produces. */
+int64_t dq_hip_window_votes_dev(int device, const uint32_t *d_regions, uint32_t n,
+                                uint32_t nregions, const uint32_t *d_offsets,
+                                const uint32_t *d_index, uint32_t total, const uint32_t *d_mapped,
+                                const uint32_t *cts /* host, nregions * k */,
+                                const uint32_t *k_outs /* host, nregions */, uint32_t k,
+                                uint32_t *d_votes /* nregions * 2 * k */,
+                                uint32_t *d_best /* nregions * 2 */, void *stream);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
