@@ -137,6 +137,11 @@ def lib():
                                 c.c_uint32, vp, vp, vp, vp, vp, vp, vp], c.c_int64),
         "dq_hip_window_votes_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, vp, vp, c.c_uint32, vp, vp, vp, c.c_uint32,
                                      vp, vp, vp], c.c_int64),
+        "dq_hip_region_containment_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, u32p, u32p, vp], c.c_int64),
+        "dq_hip_region_containment": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, vp, vp, u32p, u32p], c.c_int64),
+        "dq_hip_regions_by_size_dev": ([c.c_int, c.c_uint32, vp, vp, vp, vp], c.c_int),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -1477,6 +1482,158 @@ def window_votes_device(t_regions, num_pixels, num_regions, t_offsets, t_index, 
     if r < 0:
         raise DivQuantError("dq_hip_window_votes_dev: bad arguments")
     return int(r)
+
+
+# ---------------------------------------------------------------------------
+# Containment tree of a region map (include/dq_hip.h, "containment tree"):
+# roots touch the image border, depth is the breadth-first distance from them
+# over the edge list, the parent is the largest neighbour one level up (ties to
+# the lowest id), siblings stand in size order and `order` is the post-order:
+# the inside-out order to visit regions in.  Exact integers, independent of
+# scheduling.
+CONTAINMENT_NONE = 0xFFFFFFFF          # no parent (a root); depth, parent and pos of an orphan
+CONTAINMENT_OUTPUTS = ("depth", "parent", "roots", "child_offsets", "children", "subtree", "enclosed", "order", "pos")
+
+
+def _containment_shape(width, height, num_regions):
+    width, height, nreg = int(width), int(height), int(num_regions)
+    if not (1 <= width <= REGION_MAX_SIDE and 1 <= height <= REGION_MAX_SIDE):
+        raise ValueError("a %d x %d map: sides are 1..65535" % (width, height))
+    if not 1 <= nreg <= width * height:
+        raise ValueError("num_regions %d for %d pixels" % (nreg, width * height))
+    return width, height, nreg
+
+
+def _containment_outputs(outputs):
+    want = tuple(CONTAINMENT_OUTPUTS if outputs is None else outputs)
+    for name in want:
+        if name not in CONTAINMENT_OUTPUTS:
+            raise ValueError("no output %r: %s" % (name, ", ".join(CONTAINMENT_OUTPUTS)))
+    if "children" in want and "child_offsets" not in want:
+        raise ValueError("children come with child_offsets")
+    return want
+
+
+def _edge_count(t_edges, num_edges):
+    if num_edges is None:
+        if t_edges is not None:
+            _elems(t_edges, 0, 4, "t_edges")
+        num_edges = 0 if t_edges is None else (t_edges.size if isinstance(t_edges, np.ndarray) else t_edges.numel()) // 2
+    nedges = _scalar32(num_edges, "num_edges")
+    if nedges:
+        if t_edges is None:
+            raise ValueError("%d edges without t_edges" % nedges)
+        _elems(t_edges, 2 * nedges, 4, "t_edges")
+    return nedges
+
+
+def region_containment_device(t_regions, width, height, num_regions, t_area, t_edges, num_edges=None, outputs=None,
+                              device=0, stream=None):
+    """The containment tree of a device-resident width x height map of region
+    ids < num_regions (contiguous, 4-byte elements).  t_area: num_regions
+    words; t_edges: num_edges x 2 ids as region_adjacency_device gives them
+    (num_edges defaults to its length / 2; None with no edge).  outputs: the
+    names wanted of CONTAINMENT_OUTPUTS (None: all).  Returns (nroots, levels,
+    reached, out): out a dict of device tensors -- "depth", "parent",
+    "subtree", "pos" (num_regions,; int32 storage of the uint32 values),
+    "enclosed" (num_regions,; int64), "roots" (nroots,), "child_offsets"
+    (num_regions + 1,), "children" (reached - nroots,) and "order" (reached,).
+    Synchronous.  ValueError for bad tensors, lengths or names (nothing runs)."""
+    width, height, nreg = _containment_shape(width, height, num_regions)
+    n = width * height
+    _elems(t_regions, n, 4, "t_regions")
+    _elems(t_area, nreg, 4, "t_area")
+    nedges = _edge_count(t_edges, num_edges)
+    want = _containment_outputs(outputs)
+    import torch
+    dev = f"cuda:{device}"
+    out = {name: torch.empty(nreg + (name == "child_offsets"), dtype=torch.int64 if name == "enclosed" else torch.int32,
+                             device=dev) for name in want}
+    opt = lambda name: _dptr(out[name]) if name in out else None  # noqa: E731
+    levels, reached = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    r = lib().dq_hip_region_containment_dev(device, _dptr(t_regions), width, height, nreg, _dptr(t_area), nedges,
+                                            _dptr(t_edges) if nedges else None, opt("depth"), opt("parent"),
+                                            opt("roots"), opt("child_offsets"), opt("children"), opt("subtree"),
+                                            opt("enclosed"), opt("order"), opt("pos"), ctypes.byref(levels),
+                                            ctypes.byref(reached), _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_region_containment_dev: bad arguments")
+    used = {"roots": int(r), "children": reached.value - int(r), "order": reached.value}
+    return int(r), int(levels.value), int(reached.value), {k: v[:used.get(k, v.numel())] for k, v in out.items()}
+
+
+def region_containment(regions2d, area, edges, num_regions=None):
+    """The containment tree of a host (H, W) map of region ids (integers of at
+    most 4 bytes), its areas (num_regions; None takes regions2d.max() + 1) and
+    its edge list ((E, 2) ids, or None).  Returns a dict of numpy arrays:
+    "depth", "parent", "subtree", "pos" (R,) uint32, "enclosed" (R,) uint64,
+    "roots" (nroots,), "child_offsets" (R + 1,), "children" (reached - nroots,),
+    "order" (reached,), and the ints "levels" and "reached"."""
+    reg = np.asarray(regions2d)
+    if reg.ndim != 2 or reg.size == 0:
+        raise ValueError("regions2d must be a non-empty (H, W) array")
+    if reg.dtype.kind not in "ui" or reg.dtype.itemsize > 4:
+        raise ValueError("region ids are integers of at most 4 bytes, not %s" % reg.dtype)
+    if reg.dtype.kind == "i" and reg.min() < 0:
+        raise ValueError("region ids are not negative")
+    reg = _u32(reg)
+    top = int(reg.max())
+    nreg = top + 1 if num_regions is None else int(num_regions)
+    if not top < nreg:
+        raise ValueError("num_regions %d for ids up to %d" % (nreg, top))
+    h, w = reg.shape
+    _containment_shape(w, h, nreg)
+    if area is None:
+        raise ValueError("the areas are needed: they order parents and siblings")
+    ar = _u32(area).reshape(-1)
+    if ar.size != nreg:
+        raise ValueError("%d areas for %d regions" % (ar.size, nreg))
+    ed = np.zeros((0, 2), np.uint32) if edges is None else _u32(edges)
+    if ed.size % 2 or (ed.size and ed.ndim != 2):
+        raise ValueError("edges are (E, 2) ids")
+    nedges = _scalar32(ed.size // 2, "the edge count")
+    if nedges and (int(ed.max()) >= nreg or bool((ed[:, 0] == ed[:, 1]).any())):
+        raise ValueError("an edge joins two different ids below num_regions")
+    _require_gpu()
+    out = {name: np.zeros(nreg + (name == "child_offsets"), np.uint64 if name == "enclosed" else np.uint32)
+           for name in CONTAINMENT_OUTPUTS}
+    levels, reached = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    r = lib().dq_hip_region_containment(_ptr(reg), w, h, nreg, _ptr(ar), nedges, _ptr(ed) if nedges else None,
+                                        *[_ptr(out[name]) for name in CONTAINMENT_OUTPUTS], ctypes.byref(levels),
+                                        ctypes.byref(reached))
+    if r < 0:
+        raise DivQuantError("dq_hip_region_containment: bad arguments")
+    used = {"roots": int(r), "children": reached.value - int(r), "order": reached.value}
+    out = {k: v[:used.get(k, v.size)].copy() for k, v in out.items()}
+    out["levels"], out["reached"] = int(levels.value), int(reached.value)
+    return out
+
+
+def regions_by_size_device(t_area, num_regions=None, want_order=True, want_rank=True, device=0, stream=None):
+    """The size order of num_regions areas on the device (t_area: contiguous,
+    4-byte elements; num_regions defaults to its length): area decreasing, ties
+    by id increasing.  Returns (order, rank), device tensors of num_regions
+    words (int32 storage of the uint32 values): order[i] the id at position i,
+    rank[id] its position; None for the one not wanted.  Synchronous.
+    ValueError for bad tensors or lengths (nothing runs)."""
+    _elems(t_area, 0, 4, "t_area")
+    if num_regions is None:
+        num_regions = t_area.size if isinstance(t_area, np.ndarray) else t_area.numel()
+    nreg = _scalar32(num_regions, "num_regions")
+    if nreg < 1:
+        raise ValueError("num_regions is at least 1")
+    _elems(t_area, nreg, 4, "t_area")
+    if not (want_order or want_rank):
+        raise ValueError("neither the order nor the rank is wanted")
+    import torch
+    dev = f"cuda:{device}"
+    order = torch.empty(nreg, dtype=torch.int32, device=dev) if want_order else None
+    rank = torch.empty(nreg, dtype=torch.int32, device=dev) if want_rank else None
+    r = lib().dq_hip_regions_by_size_dev(device, nreg, _dptr(t_area), _dptr(order) if want_order else None,
+                                         _dptr(rank) if want_rank else None, _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_regions_by_size_dev: bad arguments")
+    return order, rank
 
 
 # ---------------------------------------------------------------------------

@@ -24,6 +24,7 @@
 #include "../../include/quant_util.h"
 #include "dq_engine.h"
 #include "dq_adjacency.h"
+#include "dq_contain.h"
 #include "dq_merge.h"
 #include "dq_pixels.h"
 #include "dq_regions.h"
@@ -1201,6 +1202,140 @@ int64_t dq_hip_segment_labels(const void* labels, int label_bytes, uint32_t widt
                   (void*)d_edges, (void*)d_sums, (void*)o_area, (void*)o_bbox, (void*)o_first, (void*)o_sums})
     if (p) DQ_HIP(hipFreeAsync(p, st));
   return count;
+}
+
+// Containment tree of a region map (dq_contain.hip).  Every argument check
+// comes before the first HIP call.
+static bool containment_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                                const uint32_t* area, uint32_t nedges, const uint32_t* edges, const uint32_t* depth,
+                                const uint32_t* parent, const uint32_t* roots, const uint32_t* child_offsets,
+                                const uint32_t* children, const uint32_t* subtree, const uint64_t* enclosed,
+                                const uint32_t* order, const uint32_t* pos) {
+  if (!regions || !area) return false;
+  if (nedges > 0 && !edges) return false;
+  if (width == 0 || height == 0 || width > 65535u || height > 65535u) return false;
+  if (nregions == 0 || nregions > (uint64_t)width * height) return false;
+  for (const void* p : {(const void*)regions, (const void*)area, (const void*)edges, (const void*)depth,
+                        (const void*)parent, (const void*)roots, (const void*)child_offsets, (const void*)children,
+                        (const void*)subtree, (const void*)order, (const void*)pos})
+    if (((uintptr_t)p & 3u) != 0) return false;
+  if (((uintptr_t)enclosed & 7u) != 0) return false;
+  if (children && !child_offsets) return false;
+  return true;
+}
+
+struct ContainOut {
+  uint32_t *depth, *parent, *roots, *child_offsets, *children, *subtree;
+  uint64_t* enclosed;
+  uint32_t *order, *pos;
+};
+
+// Enqueues the stages on st with scratch owned by the call, copies what is
+// wanted to `to` (device or host arrays: `kind`), waits, returns nroots.  The
+// host reads the regions reached back once per level (8 bytes) and stops at a
+// level that reached nobody.
+static int64_t region_containment_on(hipStream_t st, dq::ContainArgs a, const ContainOut& to, hipMemcpyKind kind,
+                                     uint32_t* levels, uint32_t* reached) {
+  DQ_HIP(hipMallocAsync(&a.scratch, dq::contain_scratch_bytes(a.nregions), st));
+  dq::launch_contain_roots(a, st);
+  DQ_HIP(hipGetLastError());
+  uint32_t words[2] = {0, 0};   // reached so far, the OR of the areas
+  DQ_HIP(hipMemcpyAsync(words, dq::contain_counters(a), 8, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  const uint32_t nroots = words[0], area_bits = dq::sort_key_bits(words[1]);
+  // Every level but the last reaches at least one region: at most nregions levels, the loop ends by itself.
+  uint32_t nlevels = 1, have = nroots;
+  while (a.nedges != 0 && have < a.nregions) {
+    dq::launch_contain_level(a, nlevels, st);
+    DQ_HIP(hipGetLastError());
+    DQ_HIP(hipMemcpyAsync(words, dq::contain_counters(a), 8, hipMemcpyDeviceToHost, st));
+    DQ_HIP(hipStreamSynchronize(st));
+    if (words[0] == have) break;
+    have = words[0];
+    ++nlevels;
+  }
+  dq::launch_contain_tree(a, nlevels, nroots, have, area_bits, st);
+  DQ_HIP(hipGetLastError());
+  const dq::ContainResults r = dq::contain_results(a);
+  const size_t R = a.nregions, nchildren = have - nroots;
+  // nothing behind the entries in use is written
+  if (to.depth) DQ_HIP(hipMemcpyAsync(to.depth, r.depth, R * 4, kind, st));
+  if (to.parent) DQ_HIP(hipMemcpyAsync(to.parent, r.parent, R * 4, kind, st));
+  if (to.roots && nroots) DQ_HIP(hipMemcpyAsync(to.roots, r.sequence, (size_t)nroots * 4, kind, st));
+  if (to.child_offsets) DQ_HIP(hipMemcpyAsync(to.child_offsets, r.child_offsets, (R + 1) * 4, kind, st));
+  if (to.children && nchildren) DQ_HIP(hipMemcpyAsync(to.children, r.sequence + nroots, nchildren * 4, kind, st));
+  if (to.subtree) DQ_HIP(hipMemcpyAsync(to.subtree, r.subtree, R * 4, kind, st));
+  if (to.enclosed) DQ_HIP(hipMemcpyAsync(to.enclosed, r.enclosed, R * 8, kind, st));
+  if (to.order && have) DQ_HIP(hipMemcpyAsync(to.order, r.order, (size_t)have * 4, kind, st));
+  if (to.pos) DQ_HIP(hipMemcpyAsync(to.pos, r.pos, R * 4, kind, st));
+  DQ_HIP(hipFreeAsync(a.scratch, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  if (levels) *levels = nlevels;
+  if (reached) *reached = have;
+  return (int64_t)nroots;
+}
+
+int64_t dq_hip_region_containment_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                      uint32_t nregions, const uint32_t* d_area, uint32_t nedges,
+                                      const uint32_t* d_edges, uint32_t* d_depth, uint32_t* d_parent,
+                                      uint32_t* d_roots, uint32_t* d_child_offsets, uint32_t* d_children,
+                                      uint32_t* d_subtree, uint64_t* d_enclosed, uint32_t* d_order, uint32_t* d_pos,
+                                      uint32_t* levels, uint32_t* reached, void* stream) {
+  if (!containment_args_ok(d_regions, width, height, nregions, d_area, nedges, d_edges, d_depth, d_parent, d_roots,
+                           d_child_offsets, d_children, d_subtree, d_enclosed, d_order, d_pos))
+    return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  dq::ContainArgs a{d_regions, width, height, nregions, d_area, nedges, d_edges, nullptr};
+  const ContainOut to{d_depth, d_parent, d_roots, d_child_offsets, d_children, d_subtree, d_enclosed, d_order, d_pos};
+  return region_containment_on(st, a, to, hipMemcpyDeviceToDevice, levels, reached);
+}
+
+int64_t dq_hip_region_containment(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                                  const uint32_t* area, uint32_t nedges, const uint32_t* edges, uint32_t* depth,
+                                  uint32_t* parent, uint32_t* roots, uint32_t* child_offsets, uint32_t* children,
+                                  uint32_t* subtree, uint64_t* enclosed, uint32_t* order, uint32_t* pos,
+                                  uint32_t* levels, uint32_t* reached) {
+  if (!containment_args_ok(regions, width, height, nregions, area, nedges, edges, depth, parent, roots, child_offsets,
+                           children, subtree, enclosed, order, pos))
+    return -1;
+  Engine& e = engine_for(current_device());
+  hipStream_t st = e.stream();
+  const size_t n = (size_t)width * height;
+  uint32_t *d_regions = nullptr, *d_area = nullptr, *d_edges = nullptr;
+  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
+  DQ_HIP(hipMallocAsync((void**)&d_area, (size_t)nregions * 4, st));
+  if (nedges) DQ_HIP(hipMallocAsync((void**)&d_edges, (size_t)nedges * 8, st));
+  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
+  DQ_HIP(hipMemcpyAsync(d_area, area, (size_t)nregions * 4, hipMemcpyHostToDevice, st));
+  if (nedges) DQ_HIP(hipMemcpyAsync(d_edges, edges, (size_t)nedges * 8, hipMemcpyHostToDevice, st));
+  dq::ContainArgs a{d_regions, width, height, nregions, d_area, nedges, d_edges, nullptr};
+  const ContainOut to{depth, parent, roots, child_offsets, children, subtree, enclosed, order, pos};
+  const int64_t nroots = region_containment_on(st, a, to, hipMemcpyDeviceToHost, levels, reached);
+  for (void* p : {(void*)d_regions, (void*)d_area, (void*)d_edges})
+    if (p) DQ_HIP(hipFreeAsync(p, st));
+  return nroots;
+}
+
+int dq_hip_regions_by_size_dev(int device, uint32_t nregions, const uint32_t* d_area, uint32_t* d_order,
+                               uint32_t* d_rank, void* stream) {
+  if (!d_area || nregions == 0 || (!d_order && !d_rank)) return -1;
+  for (const void* p : {(const void*)d_area, (const void*)d_order, (const void*)d_rank})
+    if (((uintptr_t)p & 3u) != 0) return -1;
+  // (no engine state is touched: calls on two streams may overlap)
+  hipStream_t st = engine_stream(device, stream);
+  void* scratch = nullptr;
+  DQ_HIP(hipMallocAsync(&scratch, dq::size_scratch_bytes(nregions), st));
+  dq::launch_size_bits(nregions, d_area, scratch, st);
+  DQ_HIP(hipGetLastError());
+  uint32_t bits = 0;   // the OR of the areas: the sort runs over the key bits in use
+  DQ_HIP(hipMemcpyAsync(&bits, dq::size_bits_word(scratch), 4, hipMemcpyDeviceToHost, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  dq::launch_size_order(nregions, d_area, dq::sort_key_bits(bits), d_order, d_rank, scratch, st);
+  DQ_HIP(hipGetLastError());
+  DQ_HIP(hipFreeAsync(scratch, st));
+  DQ_HIP(hipStreamSynchronize(st));
+  return 0;
 }
 
 // Pixel lists of a region map (dq_pixels.hip).  Every argument check comes

@@ -684,6 +684,106 @@ int64_t dq_hip_window_votes_dev(int device, const uint32_t *d_regions, uint32_t 
                                 uint32_t *d_votes /* nregions * 2 * k */,
                                 uint32_t *d_best /* nregions * 2 */, void *stream);
 
+/* ---- containment tree (region map + its graph -> which region lies in which,
+ * and the inside-out order to visit them in) ------------------------------------
+ * The reference's clusteringCombine does not visit regions in id order.  It
+ * builds a containment tree of the tag image (recurseSuperpixelContainment,
+ * ClusteringSegmentation.cpp:8545-8814: the roots are the tags that touch the
+ * image border, a tag's children the tags nested one step further in) and walks
+ * it inside-out, most deeply contained first (recurseSuperpixelIterate and a
+ * stack), handing every visit a mask of the pixels consumed so far: the optional
+ * d_mask of dq_hip_region_windows_dev.  The reference's tree is a depth-first
+ * claim: a visited tag claims all its unprocessed neighbours and blocks later
+ * siblings while it recurses, and its sibling order is an accident of an
+ * unstable sort over an unordered_set.  These entries build the data-parallel
+ * counterpart with ONE exact integer answer that does not depend on scheduling.
+ * Inputs.  d_regions: a width x height map of uint32 ids, each < nregions = R
+ * (any id map; dq_hip_label_regions_dev's is the intended one; an id >= R is
+ * passed over).  d_area[R].  nedges id pairs d_edges, (a, b) with a != b and
+ * both < R: the order within a pair, the order of the pairs and duplicates do
+ * not matter (the d_edges of dq_hip_region_adjacency_dev is the intended list;
+ * its connectivity is the caller's choice; a pair that is no such pair is
+ * skipped).
+ * Rules.
+ *   1 Roots.  r is a root when some pixel of r lies in row 0, row height - 1,
+ *     column 0 or column width - 1.  depth[r] = 0.
+ *   2 Depth.  Otherwise depth[r] = 1 + the lowest depth among r's neighbours in
+ *     the edge list: the breadth-first distance from the roots.  An id no root
+ *     reaches is an ORPHAN (ids absent from the map, ids the edge list does not
+ *     connect): depth = parent = pos = 0xFFFFFFFF, subtree = 0, enclosed = 0,
+ *     left out of roots, children and order.
+ *   3 Parent.  A root's parent is 0xFFFFFFFF.  For depth[r] > 0 the parent is,
+ *     among the neighbours q with depth[q] = depth[r] - 1, the one with the
+ *     highest area[q], ties to the lowest id (the reference walks larger regions
+ *     first, and the first to arrive claims).
+ *   4 Size order.  All R ids by area decreasing, ties by id increasing (the
+ *     reference's sortSuperpixelsBySize with its ties made definite);
+ *     rank[r] is r's position in it.
+ *   5 roots[0 .. nroots) are the roots in size order;
+ *     children[child_offsets[p] .. child_offsets[p + 1]) the regions whose
+ *     parent is p, in size order; child_offsets has R + 1 words and
+ *     child_offsets[R] = reached - nroots.
+ *   6 subtree[r] = 1 + the sum of subtree over r's children; enclosed[r]
+ *     (uint64) = area[r] + the sum of enclosed over its children.
+ *   7 Inside-out order.  order[0 .. reached) is the post-order of the forest:
+ *     the roots in root order, for each the subtrees of its children in sibling
+ *     order, then the region itself.  It equals what the reference's reversed
+ *     pre-order walk plus stack pop produces (ClusteringSegmentation.hpp:99-111,
+ *     ClusteringSegmentationMain.cpp:223-250): a pre-order over reversed sibling
+ *     lists, read backwards, is the post-order over forward lists.  In closed
+ *     form block(root i) = the sum of subtree of the roots before it,
+ *     block(child) = block(parent) + the sum of subtree of its earlier
+ *     siblings, pos[r] = block(r) + subtree[r] - 1 and order[pos[r]] = r.
+ * Agreement with the reference.  Call a map NESTED when every reached non-root
+ * region touches exactly one region of lower depth and no region of its own
+ * depth that has a different parent (rings, islands in islands, every case of
+ * Test/ContainmentTest.mm).  On nested maps parent[] and the set of roots equal
+ * the reference's containsTreeMap and rootTags whatever its sibling order
+ * happens to be.  On other maps they can differ: there the reference's answer
+ * hangs on the order in which its depth-first walk happens to claim, which
+ * nothing exact can be pinned to.
+ * Outputs, every pointer may be NULL, arrays sized by R so that no count is
+ * needed first, nothing behind the entries in use written: d_depth, d_parent,
+ * d_subtree, d_pos (R words), d_enclosed (R uint64), d_roots (nroots entries
+ * written), d_child_offsets (R + 1), d_children (reached - nroots; needs
+ * d_child_offsets), d_order (reached).  *levels (host, may be NULL) = 1 + the
+ * highest depth reached; *reached (host, may be NULL) = the non-orphans.
+ * Returns nroots >= 1, synchronous on return.  -1, before any device work, for:
+ * NULL d_regions or d_area; nedges > 0 with NULL d_edges; width or height 0 or
+ * above 65535; nregions == 0 or above width * height; a pointer not naturally
+ * aligned (4 B; 8 B for d_enclosed); d_children without d_child_offsets.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 68 B per region plus 1 KiB per
+ * 1024 regions, nothing per edge; every output is computed there and the ones
+ * asked for are copied out.  The host reads 8 bytes back per level (the regions
+ * reached so far); a tree of D levels costs about 3 D + 40 launches. */
+int64_t dq_hip_region_containment_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                      uint32_t height, uint32_t nregions, const uint32_t *d_area,
+                                      uint32_t nedges, const uint32_t *d_edges /*2 per edge*/,
+                                      uint32_t *d_depth, uint32_t *d_parent,
+                                      uint32_t *d_roots, uint32_t *d_child_offsets /*R + 1*/,
+                                      uint32_t *d_children, uint32_t *d_subtree,
+                                      uint64_t *d_enclosed, uint32_t *d_order, uint32_t *d_pos,
+                                      uint32_t *levels /*host, may be NULL*/,
+                                      uint32_t *reached /*host, may be NULL*/, void *stream);
+/* The same on host arrays, the current device: one upload (map, areas, edges),
+ * the call above, one download of the arrays asked for (as many entries of
+ * roots, children and order as are in use).  Same returns. */
+int64_t dq_hip_region_containment(const uint32_t *regions, uint32_t width, uint32_t height,
+                                  uint32_t nregions, const uint32_t *area, uint32_t nedges,
+                                  const uint32_t *edges, uint32_t *depth, uint32_t *parent,
+                                  uint32_t *roots, uint32_t *child_offsets, uint32_t *children,
+                                  uint32_t *subtree, uint64_t *enclosed, uint32_t *order,
+                                  uint32_t *pos, uint32_t *levels, uint32_t *reached);
+/* Rule 4 alone: d_order[i] = the id at position i of the size order, d_rank[id]
+ * = its position (either may be NULL, not both).  A stable LSD radix sort over
+ * the area bits in use; the host reads 4 bytes back (the OR of the areas).
+ * Returns 0, synchronous on return; -1, before any device work, for NULL
+ * d_area, nregions == 0, both outputs NULL or a misaligned pointer.  Scratch in
+ * stream order, no engine state: 20 B per region plus 1 KiB per 1024 regions. */
+int dq_hip_regions_by_size_dev(int device, uint32_t nregions, const uint32_t *d_area,
+                               uint32_t *d_order, uint32_t *d_rank, void *stream);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
