@@ -1,5 +1,6 @@
 // dq_abi.cpp -- the exported surface of libdivquant_hip.so:
-//   * the C ABI of include/dq_hip.h (device- and host-pointer entry points);
+//   * the C ABI of include/dq_hip.h (device- and host-pointer entry points;
+//     the region-map pipeline's are in dq_abi_regions.cpp);
 //   * the reference signatures of include/DivQuantHeader.h and
 //     include/quant_util.h, implemented on top of it.
 // The product path has no CPU fallback: without a HIP device every compute
@@ -22,34 +23,23 @@
 #include "../../include/DivQuantHeader.h"
 #include "../../include/dq_hip.h"
 #include "../../include/quant_util.h"
+#include "dq_abi_util.h"
 #include "dq_engine.h"
-#include "dq_adjacency.h"
-#include "dq_contain.h"
-#include "dq_merge.h"
-#include "dq_pixels.h"
-#include "dq_regions.h"
 #include "dq_weighted.h"
-#include "dq_windows.h"
-#include "dq_wtags.h"
 
 #include <rccl/rccl.h>
 #include <map>
 #include <tuple>
 
+using dq::current_device;
+using dq::dev_stream;
 using dq::Engine;
 using dq::engine_for;
+using dq::engine_stream;
+using dq::events;
+using dq::join_default_stream;
 
 namespace {
-
-int current_device() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-    dq::die("no HIP device", __FILE__, __LINE__,
-            "libdivquant_hip has no CPU fallback; run on an MI355X (gfx950)");
-  int d = 0;
-  DQ_HIP(hipGetDevice(&d));
-  return d;
-}
 
 bool quiet() {
   const char* q = std::getenv("DQ_HIP_QUIET");
@@ -129,66 +119,6 @@ class LaneWorkers {
   std::vector<std::thread> threads_;
 };
 
-// Events for one-shot cross-stream joins (a call's "inputs ready" mark, a
-// NULL-stream call's completion), one per use: concurrent calls never share
-// one (an event re-recorded by another call before a stream waited on it
-// would order the wait after the wrong work).  A stream wait captures the
-// event's state when it is enqueued, so the event returns to the pool as
-// soon as every wait on it has been enqueued.
-class EventPool {
- public:
-  hipEvent_t get() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (!free_.empty()) {
-        hipEvent_t e = free_.back();
-        free_.pop_back();
-        return e;
-      }
-    }
-    hipEvent_t e = nullptr;
-    DQ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return e;
-  }
-  void put(hipEvent_t e) {
-    std::lock_guard<std::mutex> g(mu_);
-    free_.push_back(e);
-  }
-
- private:
-  std::mutex mu_;
-  std::vector<hipEvent_t> free_;
-};
-
-EventPool& events() {
-  static EventPool* p = new EventPool();   // (never destroyed, like the engines)
-  return *p;
-}
-
-// The stream a device-pointer entry runs on: the caller's, or (NULL) the
-// engine's non-blocking stream made to wait for the legacy default stream
-// first -- the caller's inputs may still be in flight there (a torch
-// host-to-device copy on the default stream, say).
-hipStream_t dev_stream(Engine& e, void* stream) {
-  if (stream) return (hipStream_t)stream;
-  hipEvent_t ev = events().get();
-  DQ_HIP(hipEventRecord(ev, nullptr));
-  DQ_HIP(hipStreamWaitEvent(e.stream(), ev, 0));
-  events().put(ev);
-  return e.stream();
-}
-
-// An asynchronous entry called with stream NULL ran on the engine's stream:
-// order the legacy default stream after it, so work the caller queues there
-// next (a framework's copy of the outputs) sees the results.
-void join_default_stream(void* stream, hipStream_t used) {
-  if (stream) return;
-  hipEvent_t ev = events().get();
-  DQ_HIP(hipEventRecord(ev, used));
-  DQ_HIP(hipStreamWaitEvent(nullptr, ev, 0));
-  events().put(ev);
-}
-
 LaneWorkers& lane_workers() {
   static LaneWorkers* w = new LaneWorkers();   // (never destroyed: its threads are detached)
   return *w;
@@ -267,8 +197,6 @@ int dq_hip_quant_weighted_regions_dev(int device, int nregions, const uint32_t* 
   }
   return empty;
 }
-
-static hipStream_t engine_stream(int device, void* stream);
 
 int dq_hip_varpart_dev(int device, const uint32_t* d_in, uint32_t n, uint32_t rows, uint32_t cols,
                        uint32_t* k, uint32_t* ct, int num_bits, int dec_factor, int max_iters,
@@ -353,12 +281,6 @@ int dq_hip_block_hist_dev(int device, const uint32_t* d_in, uint32_t width, uint
 static bool bgr24_shape_ok(uint32_t width, uint32_t height, uint32_t stride) {
   return width > 0 && height > 0 && width <= 0xFFFFFFFFu / 3u && stride >= 3u * width &&
          (uint64_t)width * height <= 0xFFFFFFFFull;
-}
-
-static hipStream_t engine_stream(int device, void* stream) {
-  Engine& e = engine_for(device);
-  DQ_HIP(hipSetDevice(device));
-  return dev_stream(e, stream);
 }
 
 int dq_hip_pack_bgr24_dev(int device, const uint8_t* d_bgr, uint32_t width, uint32_t height,
@@ -872,1108 +794,6 @@ int dq_hip_quant_labels(const uint32_t* in, uint32_t n, void* labels, int label_
   return j.num_empty;
 }
 
-// Connected regions of a label map (dq_regions.hip).  Every argument check
-// comes before the first HIP call.
-static bool regions_args_ok(const void* labels, int label_bytes, uint32_t width, uint32_t height,
-                            int connectivity, const uint32_t* regions, uint32_t stats_cap,
-                            const uint32_t* area, const uint32_t* bbox, const uint32_t* first,
-                            const uint32_t* label, const uint32_t* pixels, const uint64_t* sums) {
-  if (label_bytes != 1 && label_bytes != 2 && label_bytes != 4) return false;
-  if (connectivity != 4 && connectivity != 8) return false;
-  if (width == 0 || height == 0 || width > 65535u || height > 65535u ||
-      (uint64_t)width * height > 0x7FFFFFFFull)
-    return false;
-  if (!labels || !regions) return false;
-  if (((uintptr_t)labels & (uintptr_t)(label_bytes - 1)) != 0) return false;
-  for (const void* p : {(const void*)regions, (const void*)area, (const void*)bbox, (const void*)first,
-                        (const void*)label, (const void*)pixels})
-    if (((uintptr_t)p & 3u) != 0) return false;
-  if (((uintptr_t)sums & 7u) != 0) return false;
-  if (sums && !pixels) return false;
-  if (stats_cap > 0 && !area && !bbox && !first && !label && !sums) return false;
-  return true;
-}
-
-// Enqueues the passes on st with scratch owned by the call, waits, returns R.
-static int64_t label_regions_on(hipStream_t st, const void* d_labels, int label_bytes, uint32_t width,
-                                uint32_t height, int connectivity, uint32_t* d_regions, uint32_t stats_cap,
-                                uint32_t* d_area, uint32_t* d_bbox, uint32_t* d_first, uint32_t* d_label,
-                                const uint32_t* d_pixels, uint64_t* d_sums) {
-  uint32_t* scratch = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&scratch, dq::region_scratch_words(width, height) * 4, st));
-  dq::RegionArgs a{d_labels, label_bytes, width,   height,   connectivity, d_regions, stats_cap,
-                   d_area,   d_bbox,      d_first, d_label, d_pixels,     (unsigned long long*)d_sums, scratch};
-  dq::launch_label_regions(a, st);
-  DQ_HIP(hipGetLastError());
-  uint32_t count = 0;
-  DQ_HIP(hipMemcpyAsync(&count, dq::region_count_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipFreeAsync(scratch, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return (int64_t)count;
-}
-
-int64_t dq_hip_label_regions_dev(int device, const void* d_labels, int label_bytes, uint32_t width,
-                                 uint32_t height, int connectivity, uint32_t* d_regions, uint32_t stats_cap,
-                                 uint32_t* d_area, uint32_t* d_bbox, uint32_t* d_first, uint32_t* d_label,
-                                 const uint32_t* d_pixels, uint64_t* d_sums, void* stream) {
-  if (!regions_args_ok(d_labels, label_bytes, width, height, connectivity, d_regions, stats_cap, d_area,
-                       d_bbox, d_first, d_label, d_pixels, d_sums))
-    return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  return label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions, stats_cap, d_area,
-                          d_bbox, d_first, d_label, d_pixels, d_sums);
-}
-
-int64_t dq_hip_label_regions(const void* labels, int label_bytes, uint32_t width, uint32_t height,
-                             int connectivity, uint32_t* regions, uint32_t stats_cap, uint32_t* area,
-                             uint32_t* bbox, uint32_t* first, uint32_t* label, const uint32_t* pixels,
-                             uint64_t* sums) {
-  if (!regions_args_ok(labels, label_bytes, width, height, connectivity, regions, stats_cap, area, bbox, first,
-                       label, pixels, sums))
-    return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height, cap = stats_cap;
-  void* d_labels = nullptr;
-  uint32_t *d_regions = nullptr, *d_area = nullptr, *d_bbox = nullptr, *d_first = nullptr, *d_label = nullptr,
-           *d_pixels = nullptr;
-  uint64_t* d_sums = nullptr;
-  DQ_HIP(hipMallocAsync(&d_labels, n * (size_t)label_bytes, st));
-  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
-  if (cap && area) DQ_HIP(hipMallocAsync((void**)&d_area, cap * 4, st));
-  if (cap && bbox) DQ_HIP(hipMallocAsync((void**)&d_bbox, cap * 16, st));
-  if (cap && first) DQ_HIP(hipMallocAsync((void**)&d_first, cap * 4, st));
-  if (cap && label) DQ_HIP(hipMallocAsync((void**)&d_label, cap * 4, st));
-  if (cap && sums) DQ_HIP(hipMallocAsync((void**)&d_sums, cap * 24, st));
-  if (cap && sums) {
-    DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
-    DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
-  }
-  DQ_HIP(hipMemcpyAsync(d_labels, labels, n * (size_t)label_bytes, hipMemcpyHostToDevice, st));
-  const int64_t count = label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions,
-                                         stats_cap, d_area, d_bbox, d_first, d_label, d_pixels, d_sums);
-  // nothing behind entry min(R, stats_cap) is written
-  const size_t m = std::min((size_t)count, cap);
-  DQ_HIP(hipMemcpyAsync(regions, d_regions, n * 4, hipMemcpyDeviceToHost, st));
-  if (d_area && m) DQ_HIP(hipMemcpyAsync(area, d_area, m * 4, hipMemcpyDeviceToHost, st));
-  if (d_bbox && m) DQ_HIP(hipMemcpyAsync(bbox, d_bbox, m * 16, hipMemcpyDeviceToHost, st));
-  if (d_first && m) DQ_HIP(hipMemcpyAsync(first, d_first, m * 4, hipMemcpyDeviceToHost, st));
-  if (d_label && m) DQ_HIP(hipMemcpyAsync(label, d_label, m * 4, hipMemcpyDeviceToHost, st));
-  if (d_sums && m) DQ_HIP(hipMemcpyAsync(sums, d_sums, m * 24, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  for (void* p : {d_labels, (void*)d_regions, (void*)d_area, (void*)d_bbox, (void*)d_first, (void*)d_label,
-                  (void*)d_pixels, (void*)d_sums})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return count;
-}
-
-// Region adjacency graph of a region map (dq_adjacency.hip).  Every argument
-// check comes before the first HIP call.
-static bool adjacency_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, int connectivity,
-                              uint32_t edge_cap, const uint32_t* edges, const uint32_t* border,
-                              const uint32_t* contact, const uint32_t* pixels, const uint64_t* step,
-                              uint32_t nregions, const uint32_t* degree) {
-  if (connectivity != 4 && connectivity != 8) return false;
-  // n <= 2^30: a contact is the one word 4 * p + dir, and E < 4 n fits uint32
-  if (width == 0 || height == 0 || width > 65535u || height > 65535u ||
-      (uint64_t)width * height > DQ_HIP_ADJACENCY_MAX_PIXELS)
-    return false;
-  if (!regions) return false;
-  for (const void* p : {(const void*)regions, (const void*)edges, (const void*)border, (const void*)contact,
-                        (const void*)pixels, (const void*)degree})
-    if (((uintptr_t)p & 3u) != 0) return false;
-  if (((uintptr_t)step & 7u) != 0) return false;
-  if (step && !pixels) return false;
-  if (edge_cap > 0 && !edges && !border && !contact && !step) return false;
-  if (degree && nregions == 0) return false;
-  return true;
-}
-
-// Enqueues both halves on st with scratch owned by the call, waits, returns E.
-// One small read-back sits between the halves: the table is sized from the
-// heads the first half counted.
-static int64_t region_adjacency_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                   int connectivity, uint32_t edge_cap, uint32_t* d_edges, uint32_t* d_border,
-                                   uint32_t* d_contact, const uint32_t* d_pixels, uint64_t* d_step,
-                                   uint32_t nregions, uint32_t* d_degree) {
-  uint32_t* counts = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&counts, dq::adjacency_count_words(width, height) * 4, st));
-  dq::AdjacencyArgs a{d_regions, width,    height,   connectivity,
-                      edge_cap,  d_edges,  d_border, d_contact,
-                      d_pixels,  (unsigned long long*)d_step, d_degree, counts, nullptr};
-  if (d_degree) DQ_HIP(hipMemsetAsync(d_degree, 0, (size_t)nregions * 4, st));
-  dq::launch_adjacency_count(a, st);
-  DQ_HIP(hipGetLastError());
-  uint32_t heads = 0, count = 0;
-  DQ_HIP(hipMemcpyAsync(&heads, dq::adjacency_heads_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  if (heads != 0) {   // (no head: no contact, no edge)
-    DQ_HIP(hipMallocAsync(&a.table, dq::adjacency_scratch_bytes(heads, d_step != nullptr), st));
-    dq::launch_adjacency_build(a, heads, st);
-    DQ_HIP(hipGetLastError());
-    DQ_HIP(hipMemcpyAsync(&count, dq::adjacency_edges_word(a), 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipFreeAsync(a.table, st));
-  }
-  DQ_HIP(hipFreeAsync(counts, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return (int64_t)count;
-}
-
-int64_t dq_hip_region_adjacency_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                    int connectivity, uint32_t edge_cap, uint32_t* d_edges, uint32_t* d_border,
-                                    uint32_t* d_contact, const uint32_t* d_pixels, uint64_t* d_step,
-                                    uint32_t nregions, uint32_t* d_degree, void* stream) {
-  if (!adjacency_args_ok(d_regions, width, height, connectivity, edge_cap, d_edges, d_border, d_contact, d_pixels,
-                         d_step, nregions, d_degree))
-    return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  return region_adjacency_on(st, d_regions, width, height, connectivity, edge_cap, d_edges, d_border, d_contact,
-                             d_pixels, d_step, nregions, d_degree);
-}
-
-int64_t dq_hip_region_adjacency(const uint32_t* regions, uint32_t width, uint32_t height, int connectivity,
-                                uint32_t edge_cap, uint32_t* edges, uint32_t* border, uint32_t* contact,
-                                const uint32_t* pixels, uint64_t* step, uint32_t nregions, uint32_t* degree) {
-  if (!adjacency_args_ok(regions, width, height, connectivity, edge_cap, edges, border, contact, pixels, step,
-                         nregions, degree))
-    return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height, cap = edge_cap;
-  uint32_t *d_regions = nullptr, *d_edges = nullptr, *d_border = nullptr, *d_contact = nullptr, *d_pixels = nullptr,
-           *d_degree = nullptr;
-  uint64_t* d_step = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
-  if (cap && edges) DQ_HIP(hipMallocAsync((void**)&d_edges, cap * 8, st));
-  if (cap && border) DQ_HIP(hipMallocAsync((void**)&d_border, cap * 4, st));
-  if (cap && contact) DQ_HIP(hipMallocAsync((void**)&d_contact, cap * 8, st));
-  if (cap && step) {
-    DQ_HIP(hipMallocAsync((void**)&d_step, cap * 8, st));
-    DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
-    DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
-  }
-  if (degree) DQ_HIP(hipMallocAsync((void**)&d_degree, (size_t)nregions * 4, st));
-  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
-  const int64_t count = region_adjacency_on(st, d_regions, width, height, connectivity, edge_cap, d_edges, d_border,
-                                            d_contact, d_pixels, d_step, nregions, d_degree);
-  // nothing behind entry min(E, edge_cap) is written
-  const size_t m = std::min((size_t)count, cap);
-  if (d_edges && m) DQ_HIP(hipMemcpyAsync(edges, d_edges, m * 8, hipMemcpyDeviceToHost, st));
-  if (d_border && m) DQ_HIP(hipMemcpyAsync(border, d_border, m * 4, hipMemcpyDeviceToHost, st));
-  if (d_contact && m) DQ_HIP(hipMemcpyAsync(contact, d_contact, m * 8, hipMemcpyDeviceToHost, st));
-  if (d_step && m) DQ_HIP(hipMemcpyAsync(step, d_step, m * 8, hipMemcpyDeviceToHost, st));
-  if (d_degree) DQ_HIP(hipMemcpyAsync(degree, d_degree, (size_t)nregions * 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  for (void* p : {(void*)d_regions, (void*)d_edges, (void*)d_border, (void*)d_contact, (void*)d_pixels,
-                  (void*)d_step, (void*)d_degree})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return count;
-}
-
-// Region merge over the adjacency graph (dq_merge.hip).  Every argument check
-// comes before the first HIP call.
-static bool merge_args_ok(const uint32_t* regions, uint32_t n, uint32_t nregions, const uint32_t* area,
-                          const uint32_t* first, const uint64_t* sums, const uint32_t* bbox, uint32_t nedges,
-                          const uint32_t* edges, const uint32_t* out_regions, const uint32_t* remap,
-                          uint32_t stats_cap, const uint32_t* out_area, const uint32_t* out_bbox,
-                          const uint32_t* out_first, const uint64_t* out_sums) {
-  if (!regions || !area || !first || !sums || !out_regions) return false;
-  if (n == 0 || n > 0x7FFFFFFFu) return false;
-  if (nregions == 0 || nregions > n) return false;
-  if (nedges > 0 && !edges) return false;
-  for (const void* p : {(const void*)regions, (const void*)area, (const void*)first, (const void*)bbox,
-                        (const void*)edges, (const void*)out_regions, (const void*)remap, (const void*)out_area,
-                        (const void*)out_bbox, (const void*)out_first})
-    if (((uintptr_t)p & 3u) != 0) return false;
-  if (((uintptr_t)sums & 7u) != 0 || ((uintptr_t)out_sums & 7u) != 0) return false;
-  if (out_bbox && !bbox) return false;
-  if (stats_cap > 0 && !out_area && !out_bbox && !out_first && !out_sums) return false;
-  return true;
-}
-
-// Enqueues the rounds on st with scratch owned by the call, waits, returns R'.
-// The host reads the links of a round back (4 bytes) and stops at 0.
-static int64_t merge_regions_on(hipStream_t st, dq::MergeArgs a, uint32_t max_rounds, uint32_t* rounds) {
-  DQ_HIP(hipMallocAsync(&a.scratch, dq::merge_scratch_bytes(a.n, a.nregions, a.bbox != nullptr, a.remap != nullptr),
-                        st));
-  dq::launch_merge_init(a, st);
-  uint32_t done = 0;
-  // Every counted round makes a link, i.e. removes at least one component: fewer than nregions rounds,
-  // so the loop ends by itself.  (Without a distance limit the restless components at least halve per
-  // round; with one, a component may get its first offer only after a neighbour's mean has moved, and
-  // a star of such leaves takes a round per leaf.)
-  while (a.nedges != 0 && a.min_area != 0 && (max_rounds == 0 || done < max_rounds)) {
-    dq::launch_merge_choose(a, st);
-    DQ_HIP(hipGetLastError());
-    uint32_t links = 0;
-    DQ_HIP(hipMemcpyAsync(&links, dq::merge_links_word(a), 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-    if (links == 0) break;
-    dq::launch_merge_fold(a, st);
-    ++done;
-  }
-  DQ_HIP(dq::launch_merge_finish(a, st));
-  DQ_HIP(hipGetLastError());
-  uint32_t count = 0;
-  DQ_HIP(hipMemcpyAsync(&count, dq::merge_count_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipFreeAsync(a.scratch, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  if (rounds) *rounds = done;
-  return (int64_t)count;
-}
-
-int64_t dq_hip_merge_regions_dev(int device, const uint32_t* d_regions, uint32_t n, uint32_t nregions,
-                                 const uint32_t* d_area, const uint32_t* d_first, const uint64_t* d_sums,
-                                 const uint32_t* d_bbox, uint32_t nedges, const uint32_t* d_edges, uint32_t min_area,
-                                 uint32_t max_dist, uint32_t max_rounds, uint32_t* d_out_regions, uint32_t* d_remap,
-                                 uint32_t stats_cap, uint32_t* d_out_area, uint32_t* d_out_bbox,
-                                 uint32_t* d_out_first, uint64_t* d_out_sums, uint32_t* rounds, void* stream) {
-  if (!merge_args_ok(d_regions, n, nregions, d_area, d_first, d_sums, d_bbox, nedges, d_edges, d_out_regions, d_remap,
-                     stats_cap, d_out_area, d_out_bbox, d_out_first, d_out_sums))
-    return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  dq::MergeArgs a{d_regions, n,        nregions,      d_area,  d_first,   (const unsigned long long*)d_sums,
-                  d_bbox,    nedges,   d_edges,       min_area, max_dist, d_out_regions,
-                  d_remap,   stats_cap, d_out_area,   d_out_bbox, d_out_first, (unsigned long long*)d_out_sums,
-                  nullptr};
-  return merge_regions_on(st, a, max_rounds, rounds);
-}
-
-int64_t dq_hip_segment_labels(const void* labels, int label_bytes, uint32_t width, uint32_t height, int connectivity,
-                              const uint32_t* pixels, uint32_t min_area, uint32_t max_dist, uint32_t max_rounds,
-                              uint32_t* regions, uint32_t stats_cap, uint32_t* area, uint32_t* bbox, uint32_t* first,
-                              uint64_t* sums, uint32_t* rounds) {
-  if (!pixels ||
-      !regions_args_ok(labels, label_bytes, width, height, connectivity, regions, stats_cap, area, bbox, first,
-                       nullptr, pixels, sums) ||
-      !adjacency_args_ok(regions, width, height, connectivity, 0, nullptr, nullptr, nullptr, pixels, nullptr, 0,
-                         nullptr))
-    return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height;
-  void* d_labels = nullptr;
-  uint32_t *d_pixels = nullptr, *d_regions = nullptr, *d_area = nullptr, *d_first = nullptr, *d_bbox = nullptr,
-           *d_edges = nullptr, *o_area = nullptr, *o_bbox = nullptr, *o_first = nullptr;
-  uint64_t *d_sums = nullptr, *o_sums = nullptr;
-  DQ_HIP(hipMallocAsync(&d_labels, n * (size_t)label_bytes, st));
-  DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
-  DQ_HIP(hipMemcpyAsync(d_labels, labels, n * (size_t)label_bytes, hipMemcpyHostToDevice, st));
-  DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
-  // R and E are known only after their stages ran: count-only, then with exact capacity
-  const int64_t R = label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions, 0, nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr);
-  DQ_HIP(hipMallocAsync((void**)&d_area, (size_t)R * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_first, (size_t)R * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_sums, (size_t)R * 24, st));
-  if (stats_cap && bbox) DQ_HIP(hipMallocAsync((void**)&d_bbox, (size_t)R * 16, st));
-  label_regions_on(st, d_labels, label_bytes, width, height, connectivity, d_regions, (uint32_t)R, d_area, d_bbox,
-                   d_first, nullptr, d_pixels, d_sums);
-  const int64_t E = region_adjacency_on(st, d_regions, width, height, connectivity, 0, nullptr, nullptr, nullptr,
-                                        nullptr, nullptr, 0, nullptr);
-  if (E > 0) {
-    DQ_HIP(hipMallocAsync((void**)&d_edges, (size_t)E * 8, st));
-    region_adjacency_on(st, d_regions, width, height, connectivity, (uint32_t)E, d_edges, nullptr, nullptr, nullptr,
-                        nullptr, 0, nullptr);
-  }
-  const size_t cap = std::min((size_t)stats_cap, (size_t)R);   // (R' <= R)
-  if (cap && area) DQ_HIP(hipMallocAsync((void**)&o_area, cap * 4, st));
-  if (cap && bbox) DQ_HIP(hipMallocAsync((void**)&o_bbox, cap * 16, st));
-  if (cap && first) DQ_HIP(hipMallocAsync((void**)&o_first, cap * 4, st));
-  if (cap && sums) DQ_HIP(hipMallocAsync((void**)&o_sums, cap * 24, st));
-  dq::MergeArgs a{d_regions, (uint32_t)n,   (uint32_t)R, d_area,   d_first,  (const unsigned long long*)d_sums,
-                  d_bbox,    (uint32_t)E,   d_edges,     min_area, max_dist, d_regions,
-                  nullptr,   (uint32_t)cap, o_area,      o_bbox,   o_first,  (unsigned long long*)o_sums,
-                  nullptr};
-  const int64_t count = merge_regions_on(st, a, max_rounds, rounds);
-  // nothing behind entry min(R', stats_cap) is written
-  const size_t m = std::min((size_t)count, cap);
-  DQ_HIP(hipMemcpyAsync(regions, d_regions, n * 4, hipMemcpyDeviceToHost, st));
-  if (o_area && m) DQ_HIP(hipMemcpyAsync(area, o_area, m * 4, hipMemcpyDeviceToHost, st));
-  if (o_bbox && m) DQ_HIP(hipMemcpyAsync(bbox, o_bbox, m * 16, hipMemcpyDeviceToHost, st));
-  if (o_first && m) DQ_HIP(hipMemcpyAsync(first, o_first, m * 4, hipMemcpyDeviceToHost, st));
-  if (o_sums && m) DQ_HIP(hipMemcpyAsync(sums, o_sums, m * 24, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  for (void* p : {d_labels, (void*)d_pixels, (void*)d_regions, (void*)d_area, (void*)d_first, (void*)d_bbox,
-                  (void*)d_edges, (void*)d_sums, (void*)o_area, (void*)o_bbox, (void*)o_first, (void*)o_sums})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return count;
-}
-
-// Containment tree of a region map (dq_contain.hip).  Every argument check
-// comes before the first HIP call.
-static bool containment_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                                const uint32_t* area, uint32_t nedges, const uint32_t* edges, const uint32_t* depth,
-                                const uint32_t* parent, const uint32_t* roots, const uint32_t* child_offsets,
-                                const uint32_t* children, const uint32_t* subtree, const uint64_t* enclosed,
-                                const uint32_t* order, const uint32_t* pos) {
-  if (!regions || !area) return false;
-  if (nedges > 0 && !edges) return false;
-  if (width == 0 || height == 0 || width > 65535u || height > 65535u) return false;
-  if (nregions == 0 || nregions > (uint64_t)width * height) return false;
-  for (const void* p : {(const void*)regions, (const void*)area, (const void*)edges, (const void*)depth,
-                        (const void*)parent, (const void*)roots, (const void*)child_offsets, (const void*)children,
-                        (const void*)subtree, (const void*)order, (const void*)pos})
-    if (((uintptr_t)p & 3u) != 0) return false;
-  if (((uintptr_t)enclosed & 7u) != 0) return false;
-  if (children && !child_offsets) return false;
-  return true;
-}
-
-struct ContainOut {
-  uint32_t *depth, *parent, *roots, *child_offsets, *children, *subtree;
-  uint64_t* enclosed;
-  uint32_t *order, *pos;
-};
-
-// Enqueues the stages on st with scratch owned by the call, copies what is
-// wanted to `to` (device or host arrays: `kind`), waits, returns nroots.  The
-// host reads the regions reached back once per level (8 bytes) and stops at a
-// level that reached nobody.
-static int64_t region_containment_on(hipStream_t st, dq::ContainArgs a, const ContainOut& to, hipMemcpyKind kind,
-                                     uint32_t* levels, uint32_t* reached) {
-  DQ_HIP(hipMallocAsync(&a.scratch, dq::contain_scratch_bytes(a.nregions), st));
-  dq::launch_contain_roots(a, st);
-  DQ_HIP(hipGetLastError());
-  uint32_t words[2] = {0, 0};   // reached so far, the OR of the areas
-  DQ_HIP(hipMemcpyAsync(words, dq::contain_counters(a), 8, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  const uint32_t nroots = words[0], area_bits = dq::sort_key_bits(words[1]);
-  // Every level but the last reaches at least one region: at most nregions levels, the loop ends by itself.
-  uint32_t nlevels = 1, have = nroots;
-  while (a.nedges != 0 && have < a.nregions) {
-    dq::launch_contain_level(a, nlevels, st);
-    DQ_HIP(hipGetLastError());
-    DQ_HIP(hipMemcpyAsync(words, dq::contain_counters(a), 8, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-    if (words[0] == have) break;
-    have = words[0];
-    ++nlevels;
-  }
-  dq::launch_contain_tree(a, nlevels, nroots, have, area_bits, st);
-  DQ_HIP(hipGetLastError());
-  const dq::ContainResults r = dq::contain_results(a);
-  const size_t R = a.nregions, nchildren = have - nroots;
-  // nothing behind the entries in use is written
-  if (to.depth) DQ_HIP(hipMemcpyAsync(to.depth, r.depth, R * 4, kind, st));
-  if (to.parent) DQ_HIP(hipMemcpyAsync(to.parent, r.parent, R * 4, kind, st));
-  if (to.roots && nroots) DQ_HIP(hipMemcpyAsync(to.roots, r.sequence, (size_t)nroots * 4, kind, st));
-  if (to.child_offsets) DQ_HIP(hipMemcpyAsync(to.child_offsets, r.child_offsets, (R + 1) * 4, kind, st));
-  if (to.children && nchildren) DQ_HIP(hipMemcpyAsync(to.children, r.sequence + nroots, nchildren * 4, kind, st));
-  if (to.subtree) DQ_HIP(hipMemcpyAsync(to.subtree, r.subtree, R * 4, kind, st));
-  if (to.enclosed) DQ_HIP(hipMemcpyAsync(to.enclosed, r.enclosed, R * 8, kind, st));
-  if (to.order && have) DQ_HIP(hipMemcpyAsync(to.order, r.order, (size_t)have * 4, kind, st));
-  if (to.pos) DQ_HIP(hipMemcpyAsync(to.pos, r.pos, R * 4, kind, st));
-  DQ_HIP(hipFreeAsync(a.scratch, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  if (levels) *levels = nlevels;
-  if (reached) *reached = have;
-  return (int64_t)nroots;
-}
-
-int64_t dq_hip_region_containment_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                      uint32_t nregions, const uint32_t* d_area, uint32_t nedges,
-                                      const uint32_t* d_edges, uint32_t* d_depth, uint32_t* d_parent,
-                                      uint32_t* d_roots, uint32_t* d_child_offsets, uint32_t* d_children,
-                                      uint32_t* d_subtree, uint64_t* d_enclosed, uint32_t* d_order, uint32_t* d_pos,
-                                      uint32_t* levels, uint32_t* reached, void* stream) {
-  if (!containment_args_ok(d_regions, width, height, nregions, d_area, nedges, d_edges, d_depth, d_parent, d_roots,
-                           d_child_offsets, d_children, d_subtree, d_enclosed, d_order, d_pos))
-    return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  dq::ContainArgs a{d_regions, width, height, nregions, d_area, nedges, d_edges, nullptr};
-  const ContainOut to{d_depth, d_parent, d_roots, d_child_offsets, d_children, d_subtree, d_enclosed, d_order, d_pos};
-  return region_containment_on(st, a, to, hipMemcpyDeviceToDevice, levels, reached);
-}
-
-int64_t dq_hip_region_containment(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                                  const uint32_t* area, uint32_t nedges, const uint32_t* edges, uint32_t* depth,
-                                  uint32_t* parent, uint32_t* roots, uint32_t* child_offsets, uint32_t* children,
-                                  uint32_t* subtree, uint64_t* enclosed, uint32_t* order, uint32_t* pos,
-                                  uint32_t* levels, uint32_t* reached) {
-  if (!containment_args_ok(regions, width, height, nregions, area, nedges, edges, depth, parent, roots, child_offsets,
-                           children, subtree, enclosed, order, pos))
-    return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height;
-  uint32_t *d_regions = nullptr, *d_area = nullptr, *d_edges = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_area, (size_t)nregions * 4, st));
-  if (nedges) DQ_HIP(hipMallocAsync((void**)&d_edges, (size_t)nedges * 8, st));
-  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
-  DQ_HIP(hipMemcpyAsync(d_area, area, (size_t)nregions * 4, hipMemcpyHostToDevice, st));
-  if (nedges) DQ_HIP(hipMemcpyAsync(d_edges, edges, (size_t)nedges * 8, hipMemcpyHostToDevice, st));
-  dq::ContainArgs a{d_regions, width, height, nregions, d_area, nedges, d_edges, nullptr};
-  const ContainOut to{depth, parent, roots, child_offsets, children, subtree, enclosed, order, pos};
-  const int64_t nroots = region_containment_on(st, a, to, hipMemcpyDeviceToHost, levels, reached);
-  for (void* p : {(void*)d_regions, (void*)d_area, (void*)d_edges})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return nroots;
-}
-
-int dq_hip_regions_by_size_dev(int device, uint32_t nregions, const uint32_t* d_area, uint32_t* d_order,
-                               uint32_t* d_rank, void* stream) {
-  if (!d_area || nregions == 0 || (!d_order && !d_rank)) return -1;
-  for (const void* p : {(const void*)d_area, (const void*)d_order, (const void*)d_rank})
-    if (((uintptr_t)p & 3u) != 0) return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  void* scratch = nullptr;
-  DQ_HIP(hipMallocAsync(&scratch, dq::size_scratch_bytes(nregions), st));
-  dq::launch_size_bits(nregions, d_area, scratch, st);
-  DQ_HIP(hipGetLastError());
-  uint32_t bits = 0;   // the OR of the areas: the sort runs over the key bits in use
-  DQ_HIP(hipMemcpyAsync(&bits, dq::size_bits_word(scratch), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  dq::launch_size_order(nregions, d_area, dq::sort_key_bits(bits), d_order, d_rank, scratch, st);
-  DQ_HIP(hipGetLastError());
-  DQ_HIP(hipFreeAsync(scratch, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return 0;
-}
-
-// Pixel lists of a region map (dq_pixels.hip).  Every argument check comes
-// before the first HIP call.
-static bool pixels_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                           const uint32_t* offsets, const uint32_t* coords, const uint32_t* index,
-                           const uint32_t* pixels, const uint32_t* colors) {
-  if (!regions || !offsets) return false;
-  if (width == 0 || height == 0 || width > 65535u || height > 65535u || (uint64_t)width * height > 0x7FFFFFFFull)
-    return false;
-  if (nregions == 0 || nregions > 0x7FFFFFFFu) return false;
-  for (const void* p : {(const void*)regions, (const void*)offsets, (const void*)coords, (const void*)index,
-                        (const void*)pixels, (const void*)colors})
-    if (((uintptr_t)p & 3u) != 0) return false;
-  if (colors && !pixels) return false;
-  return true;
-}
-
-// Enqueues both halves on st with scratch owned by the call and waits.  One
-// small read-back sits between the halves: the table is sized from T, and a
-// map with T > n is refused there, before any output array is written.
-static int64_t region_pixels_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                uint32_t nregions, uint32_t* d_offsets, uint32_t* d_coords, uint32_t* d_index,
-                                const uint32_t* d_pixels, uint32_t* d_colors) {
-  dq::PixelsArgs a{d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels, d_colors, nullptr, nullptr};
-  DQ_HIP(hipMallocAsync((void**)&a.rows, dq::pixels_rows_bytes(nregions), st));
-  dq::launch_pixels_rows(a, st);
-  DQ_HIP(hipGetLastError());
-  uint32_t total = 0;
-  DQ_HIP(hipMemcpyAsync(&total, dq::pixels_total_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  const bool fits = total <= width * height;
-  if (fits) {
-    DQ_HIP(hipMallocAsync((void**)&a.table, dq::pixels_table_bytes(total), st));
-    dq::launch_pixels_lists(a, total, st);
-    DQ_HIP(hipGetLastError());
-    DQ_HIP(hipFreeAsync(a.table, st));
-  }
-  DQ_HIP(hipFreeAsync(a.rows, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return fits ? 0 : -2;
-}
-
-int64_t dq_hip_region_pixels_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                 uint32_t nregions, uint32_t* d_offsets, uint32_t* d_coords, uint32_t* d_index,
-                                 const uint32_t* d_pixels, uint32_t* d_colors, void* stream) {
-  if (!pixels_args_ok(d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels, d_colors)) return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  return region_pixels_on(st, d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels, d_colors);
-}
-
-int64_t dq_hip_region_pixels(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                             uint32_t* offsets, uint32_t* coords, uint32_t* index, const uint32_t* pixels,
-                             uint32_t* colors) {
-  if (!pixels_args_ok(regions, width, height, nregions, offsets, coords, index, pixels, colors)) return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
-  uint32_t *d_regions = nullptr, *d_offsets = nullptr, *d_coords = nullptr, *d_index = nullptr, *d_pixels = nullptr,
-           *d_colors = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
-  if (coords) DQ_HIP(hipMallocAsync((void**)&d_coords, n * 4, st));
-  if (index) DQ_HIP(hipMallocAsync((void**)&d_index, n * 4, st));
-  if (colors) {
-    DQ_HIP(hipMallocAsync((void**)&d_colors, n * 4, st));
-    DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
-    DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
-  }
-  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
-  const int64_t rc = region_pixels_on(st, d_regions, width, height, nregions, d_offsets, d_coords, d_index, d_pixels,
-                                      d_colors);
-  if (rc == 0) {   // (a refused map leaves the host arrays as they were)
-    DQ_HIP(hipMemcpyAsync(offsets, d_offsets, no * 4, hipMemcpyDeviceToHost, st));
-    if (coords) DQ_HIP(hipMemcpyAsync(coords, d_coords, n * 4, hipMemcpyDeviceToHost, st));
-    if (index) DQ_HIP(hipMemcpyAsync(index, d_index, n * 4, hipMemcpyDeviceToHost, st));
-    if (colors) DQ_HIP(hipMemcpyAsync(colors, d_colors, n * 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-  }
-  for (void* p : {(void*)d_regions, (void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_pixels,
-                  (void*)d_colors})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return rc;
-}
-
-int dq_hip_scatter_coords_dev(int device, const uint32_t* d_values, const uint32_t* d_coords, uint32_t n,
-                              uint32_t width, uint32_t* d_frame, void* stream) {
-  if (!d_values || !d_coords || !d_frame || width == 0) return -1;
-  for (const void* p : {(const void*)d_values, (const void*)d_coords, (const void*)d_frame})
-    if (((uintptr_t)p & 3u) != 0) return -1;
-  if (n == 0) return 0;
-  hipStream_t st = engine_stream(device, stream);
-  dq::launch_scatter_coords(d_values, d_coords, n, width, d_frame, st);
-  join_default_stream(stream, st);
-  DQ_HIP(hipGetLastError());
-  return 0;
-}
-
-// Region map -> pixel lists -> one weighted quant per region -> painted frame.
-// The regions path keeps one pinned argument and one pinned result record per
-// job of a call (about 4.5 KB): the jobs go to it kRegionMapJobs at a time.
-static constexpr size_t kRegionMapJobs = 8192;
-
-static bool region_map_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                               const uint32_t* pixels, uint32_t k, const uint32_t* out, const uint32_t* cts,
-                               const uint32_t* k_outs, int max_iters) {
-  if (!pixels || !cts || !k_outs || k == 0 || k > 0x7FFFFFFFu || max_iters < 1) return false;
-  if (((uintptr_t)out & 3u) != 0) return false;
-  // (the offsets and lists are the call's own: any aligned non-NULL pointer stands in for them)
-  return pixels_args_ok(regions, width, height, nregions, regions, nullptr, nullptr, pixels, nullptr);
-}
-
-// One weighted-regions call over the ranges [off[r], off[r + 1]) of d_colors, region r's K = k: its
-// colortable to cts + r * k, its count to k_outs[r] (0 for an empty range, the row untouched), its
-// mapped colours to the same range of d_mapped when given.  Returns the total of empty clusters.
-static int64_t quant_ranges_on(int device, hipStream_t st, const std::vector<uint32_t>& off, uint32_t nregions,
-                               const uint32_t* d_colors, uint32_t* d_mapped, uint32_t k, uint32_t* cts,
-                               uint32_t* k_outs, int max_iters) {
-  int64_t empty = 0;
-  Engine& e = engine_for(device);
-  std::vector<dq::FrameJob> jobs;
-  std::vector<uint32_t> ids;
-  jobs.reserve(std::min<size_t>(nregions, kRegionMapJobs));
-  ids.reserve(jobs.capacity());
-  auto flush = [&] {
-    if (jobs.empty()) return;
-    {
-      std::lock_guard<std::mutex> g(e.mutex());
-      e.run_weighted_regions(jobs.data(), (int)jobs.size(), max_iters, st);
-    }
-    for (size_t i = 0; i < jobs.size(); ++i) {
-      k_outs[ids[i]] = (uint32_t)jobs[i].k_out;
-      empty += jobs[i].num_empty;
-    }
-    jobs.clear();
-    ids.clear();
-  };
-  for (uint32_t r = 0; r < nregions; ++r) {
-    const uint32_t len = off[r + 1] - off[r];
-    if (len == 0) {   // an empty list: no call, its colortable row stays as it is
-      k_outs[r] = 0;
-      continue;
-    }
-    dq::FrameJob j;
-    j.d_in = d_colors + off[r];
-    j.n = len;
-    j.d_out = d_mapped ? d_mapped + off[r] : nullptr;
-    j.k = (int)k;
-    j.ct = cts + (size_t)r * k;
-    jobs.push_back(j);
-    ids.push_back(r);
-    if (jobs.size() == kRegionMapJobs) flush();
-  }
-  flush();
-  return empty;
-}
-
-static int64_t quant_region_map_on(int device, hipStream_t st, const uint32_t* d_regions, uint32_t width,
-                                   uint32_t height, uint32_t nregions, const uint32_t* d_pixels, uint32_t k,
-                                   uint32_t* d_out, uint32_t* cts, uint32_t* k_outs, int max_iters) {
-  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
-  uint32_t *d_offsets = nullptr, *d_colors = nullptr, *d_coords = nullptr, *d_mapped = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_colors, n * 4, st));
-  if (d_out) {
-    DQ_HIP(hipMallocAsync((void**)&d_coords, n * 4, st));
-    DQ_HIP(hipMallocAsync((void**)&d_mapped, n * 4, st));
-    // (an id >= nregions leaves its pixel out of the lists: the scatter below then reads Coord 0, not garbage)
-    DQ_HIP(hipMemsetAsync(d_coords, 0, n * 4, st));
-  }
-  int64_t rc = region_pixels_on(st, d_regions, width, height, nregions, d_offsets, d_coords, nullptr, d_pixels, d_colors);
-  if (rc == 0) {
-    std::vector<uint32_t> off(no);
-    DQ_HIP(hipMemcpyAsync(off.data(), d_offsets, no * 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-    rc = quant_ranges_on(device, st, off, nregions, d_colors, d_mapped, k, cts, k_outs, max_iters);
-    if (d_out) {
-      dq::launch_scatter_coords(d_mapped, d_coords, (uint32_t)n, width, d_out, st);
-      DQ_HIP(hipGetLastError());
-    }
-  }
-  for (void* p : {(void*)d_offsets, (void*)d_colors, (void*)d_coords, (void*)d_mapped})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return rc;
-}
-
-int64_t dq_hip_quant_region_map_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                    uint32_t nregions, const uint32_t* d_pixels, uint32_t k, uint32_t* d_out,
-                                    uint32_t* cts, uint32_t* k_outs, int max_iters, void* stream) {
-  if (!region_map_args_ok(d_regions, width, height, nregions, d_pixels, k, d_out, cts, k_outs, max_iters)) return -1;
-  hipStream_t st = engine_stream(device, stream);
-  return quant_region_map_on(device, st, d_regions, width, height, nregions, d_pixels, k, d_out, cts, k_outs,
-                             max_iters);
-}
-
-int64_t dq_hip_quant_region_map(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                                const uint32_t* pixels, uint32_t k, uint32_t* out, uint32_t* cts, uint32_t* k_outs,
-                                int max_iters) {
-  if (!region_map_args_ok(regions, width, height, nregions, pixels, k, out, cts, k_outs, max_iters)) return -1;
-  const int device = current_device();
-  hipStream_t st = engine_for(device).stream();
-  const size_t n = (size_t)width * height;
-  uint32_t *d_regions = nullptr, *d_pixels = nullptr, *d_out = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_regions, n * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_pixels, n * 4, st));
-  if (out) DQ_HIP(hipMallocAsync((void**)&d_out, n * 4, st));
-  DQ_HIP(hipMemcpyAsync(d_regions, regions, n * 4, hipMemcpyHostToDevice, st));
-  DQ_HIP(hipMemcpyAsync(d_pixels, pixels, n * 4, hipMemcpyHostToDevice, st));
-  const int64_t rc = quant_region_map_on(device, st, d_regions, width, height, nregions, d_pixels, k, d_out, cts,
-                                         k_outs, max_iters);
-  if (rc >= 0 && out) {
-    DQ_HIP(hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-  }
-  for (void* p : {(void*)d_regions, (void*)d_pixels, (void*)d_out})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return rc;
-}
-
-// Capture windows of a region map (dq_windows.hip).  Every argument check comes
-// before the first HIP call.
-static bool windows_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, uint32_t block,
-                            uint32_t expand, const uint32_t* area, const uint32_t* offsets, uint32_t cap,
-                            const uint32_t* coords, const uint32_t* index, const uint32_t* pixels,
-                            const uint32_t* colors) {
-  if (!pixels_args_ok(regions, width, height, nregions, offsets, coords, index, pixels, colors)) return false;
-  if (block < 1 || block > 8 || expand > 3) return false;
-  if (((uintptr_t)area & 3u) != 0) return false;
-  if (cap > 0 && !coords && !index && !colors) return false;
-  return true;
-}
-
-// Enqueues the parts on st with scratch owned by the call and waits.  Two small
-// read-backs sit between them: P and T size the pairs and the table (a map with
-// T > P is refused there), and M decides -3 and whether the lists fit, before
-// any output array is written.
-static int64_t region_windows_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                 uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
-                                 const uint32_t* d_area, uint32_t min_area, uint32_t* d_offsets, uint32_t cap,
-                                 uint32_t* d_coords, uint32_t* d_index, const uint32_t* d_pixels, uint32_t* d_colors) {
-  dq::WindowsArgs a{d_regions, width,    height,  nregions, block,    expand,   d_mask, d_area,
-                    min_area,  d_offsets, d_coords, d_index, d_pixels, d_colors, nullptr, nullptr};
-  DQ_HIP(hipMallocAsync((void**)&a.blocks, dq::windows_blocks_bytes(width, height, block, nregions), st));
-  dq::launch_windows_blocks(a, st);
-  DQ_HIP(hipGetLastError());
-  uint32_t npairs = 0, nrows = 0, total = 0;
-  DQ_HIP(hipMemcpyAsync(&npairs, dq::windows_pairs_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipMemcpyAsync(&nrows, dq::windows_rows_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  int64_t rc;
-  if (npairs == 0xFFFFFFFFu) {
-    rc = -3;   // (the pairs are indexed by words)
-  } else if (nrows > npairs) {
-    rc = -2;
-  } else {
-    DQ_HIP(hipMallocAsync((void**)&a.pairs, dq::windows_pairs_bytes(npairs, nrows), st));
-    if (npairs != 0 && nrows != 0) {
-      dq::launch_windows_count(a, npairs, nrows, st);
-      DQ_HIP(hipGetLastError());
-      DQ_HIP(hipMemcpyAsync(&total, dq::windows_total_word(a, npairs, nrows), 4, hipMemcpyDeviceToHost, st));
-      DQ_HIP(hipStreamSynchronize(st));
-    }
-    if (total == 0xFFFFFFFFu) {
-      rc = -3;
-    } else {
-      rc = total;
-      dq::launch_windows_offsets(a, npairs, nrows, total, st);
-      if (total <= cap) dq::launch_windows_lists(a, npairs, nrows, total, st);
-      DQ_HIP(hipGetLastError());
-    }
-    DQ_HIP(hipFreeAsync(a.pairs, st));
-  }
-  DQ_HIP(hipFreeAsync(a.blocks, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return rc;
-}
-
-int64_t dq_hip_region_windows_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                  uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
-                                  const uint32_t* d_area, uint32_t min_area, uint32_t* d_offsets, uint32_t cap,
-                                  uint32_t* d_coords, uint32_t* d_index, const uint32_t* d_pixels, uint32_t* d_colors,
-                                  void* stream) {
-  if (!windows_args_ok(d_regions, width, height, nregions, block, expand, d_area, d_offsets, cap, d_coords, d_index,
-                       d_pixels, d_colors))
-    return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  return region_windows_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area, d_offsets,
-                           cap, d_coords, d_index, d_pixels, d_colors);
-}
-
-// The device copies of a host windows call's inputs.
-struct WindowsInputs {
-  uint32_t *regions = nullptr, *area = nullptr, *pixels = nullptr;
-  uint8_t* mask = nullptr;
-  void upload(hipStream_t st, size_t n, uint32_t nregions, const uint32_t* h_regions, const uint8_t* h_mask,
-              const uint32_t* h_area, const uint32_t* h_pixels) {
-    DQ_HIP(hipMallocAsync((void**)&regions, n * 4, st));
-    DQ_HIP(hipMemcpyAsync(regions, h_regions, n * 4, hipMemcpyHostToDevice, st));
-    if (h_mask) {
-      DQ_HIP(hipMallocAsync((void**)&mask, n, st));
-      DQ_HIP(hipMemcpyAsync(mask, h_mask, n, hipMemcpyHostToDevice, st));
-    }
-    if (h_area) {
-      DQ_HIP(hipMallocAsync((void**)&area, (size_t)nregions * 4, st));
-      DQ_HIP(hipMemcpyAsync(area, h_area, (size_t)nregions * 4, hipMemcpyHostToDevice, st));
-    }
-    if (h_pixels) {
-      DQ_HIP(hipMallocAsync((void**)&pixels, n * 4, st));
-      DQ_HIP(hipMemcpyAsync(pixels, h_pixels, n * 4, hipMemcpyHostToDevice, st));
-    }
-  }
-  void release(hipStream_t st) {
-    for (void* p : {(void*)regions, (void*)area, (void*)pixels, (void*)mask})
-      if (p) DQ_HIP(hipFreeAsync(p, st));
-  }
-};
-
-int64_t dq_hip_region_windows(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                              uint32_t block, uint32_t expand, const uint8_t* mask, const uint32_t* area,
-                              uint32_t min_area, uint32_t* offsets, uint32_t cap, uint32_t* coords, uint32_t* index,
-                              const uint32_t* pixels, uint32_t* colors) {
-  if (!windows_args_ok(regions, width, height, nregions, block, expand, area, offsets, cap, coords, index, pixels,
-                       colors))
-    return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
-  WindowsInputs in;
-  in.upload(st, n, nregions, regions, mask, area, colors ? pixels : nullptr);
-  uint32_t *d_offsets = nullptr, *d_coords = nullptr, *d_index = nullptr, *d_colors = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
-  if (cap && coords) DQ_HIP(hipMallocAsync((void**)&d_coords, (size_t)cap * 4, st));
-  if (cap && index) DQ_HIP(hipMallocAsync((void**)&d_index, (size_t)cap * 4, st));
-  if (cap && colors) DQ_HIP(hipMallocAsync((void**)&d_colors, (size_t)cap * 4, st));
-  const int64_t rc = region_windows_on(st, in.regions, width, height, nregions, block, expand, in.mask, in.area,
-                                       min_area, d_offsets, cap, d_coords, d_index, in.pixels, d_colors);
-  if (rc >= 0) {   // (a refused map leaves the host arrays as they were)
-    DQ_HIP(hipMemcpyAsync(offsets, d_offsets, no * 4, hipMemcpyDeviceToHost, st));
-    if (rc > 0 && rc <= (int64_t)cap) {
-      if (d_coords) DQ_HIP(hipMemcpyAsync(coords, d_coords, (size_t)rc * 4, hipMemcpyDeviceToHost, st));
-      if (d_index) DQ_HIP(hipMemcpyAsync(index, d_index, (size_t)rc * 4, hipMemcpyDeviceToHost, st));
-      if (d_colors) DQ_HIP(hipMemcpyAsync(colors, d_colors, (size_t)rc * 4, hipMemcpyDeviceToHost, st));
-    }
-    DQ_HIP(hipStreamSynchronize(st));
-  }
-  in.release(st);
-  for (void* p : {(void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_colors})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return rc;
-}
-
-// Region map -> capture windows -> one weighted quant per window.
-static bool quant_windows_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                                  uint32_t block, uint32_t expand, const uint32_t* area, const uint32_t* offsets,
-                                  uint32_t cap, const uint32_t* coords, const uint32_t* index, const uint32_t* pixels,
-                                  const uint32_t* colors, uint32_t k, const uint32_t* out, const uint32_t* cts,
-                                  const uint32_t* k_outs, int max_iters) {
-  if (!pixels || !cts || !k_outs || k == 0 || k > 0x7FFFFFFFu || max_iters < 1) return false;
-  if (((uintptr_t)out & 3u) != 0) return false;
-  if (cap > 0 && !coords && !index && !colors && out) coords = out;   // (d_out alone is a list array of cap words)
-  return windows_args_ok(regions, width, height, nregions, block, expand, area, offsets, cap, coords, index, pixels,
-                         colors);
-}
-
-static int64_t quant_region_windows_on(int device, hipStream_t st, const uint32_t* d_regions, uint32_t width,
-                                       uint32_t height, uint32_t nregions, uint32_t block, uint32_t expand,
-                                       const uint8_t* d_mask, const uint32_t* d_area, uint32_t min_area,
-                                       uint32_t* d_offsets, uint32_t cap, uint32_t* d_coords, uint32_t* d_index,
-                                       const uint32_t* d_pixels, uint32_t* d_colors, uint32_t k, uint32_t* d_out,
-                                       uint32_t* cts, uint32_t* k_outs, int max_iters) {
-  const size_t no = (size_t)nregions + 1;
-  const bool lists = d_coords || d_index || d_colors;
-  int64_t rc = region_windows_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area,
-                                 d_offsets, lists ? cap : 0u, d_coords, d_index, d_pixels, d_colors);
-  if (rc < 0) return rc;
-  const int64_t total = rc;
-  if (d_out && total > (int64_t)cap) return -4;
-  // the colours in list order: the caller's when they were written, else the call's own
-  uint32_t *own_offsets = nullptr, *own_colors = nullptr;
-  const uint32_t* colors = d_colors;
-  if (!(d_colors && total <= (int64_t)cap) && total > 0) {
-    DQ_HIP(hipMallocAsync((void**)&own_offsets, no * 4, st));
-    DQ_HIP(hipMallocAsync((void**)&own_colors, (size_t)total * 4, st));
-    rc = region_windows_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area,
-                           own_offsets, (uint32_t)total, nullptr, nullptr, d_pixels, own_colors);
-    colors = own_colors;
-  }
-  if (rc >= 0) {
-    std::vector<uint32_t> off(no);
-    DQ_HIP(hipMemcpyAsync(off.data(), d_offsets, no * 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-    rc = quant_ranges_on(device, st, off, nregions, colors, d_out, k, cts, k_outs, max_iters);
-  }
-  for (void* p : {(void*)own_offsets, (void*)own_colors})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return rc;
-}
-
-int64_t dq_hip_quant_region_windows_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                                        uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
-                                        const uint32_t* d_area, uint32_t min_area, uint32_t* d_offsets, uint32_t cap,
-                                        uint32_t* d_coords, uint32_t* d_index, const uint32_t* d_pixels,
-                                        uint32_t* d_colors, uint32_t k, uint32_t* d_out, uint32_t* cts,
-                                        uint32_t* k_outs, int max_iters, void* stream) {
-  if (!quant_windows_args_ok(d_regions, width, height, nregions, block, expand, d_area, d_offsets, cap, d_coords,
-                             d_index, d_pixels, d_colors, k, d_out, cts, k_outs, max_iters))
-    return -1;
-  hipStream_t st = engine_stream(device, stream);
-  return quant_region_windows_on(device, st, d_regions, width, height, nregions, block, expand, d_mask, d_area,
-                                 min_area, d_offsets, cap, d_coords, d_index, d_pixels, d_colors, k, d_out, cts, k_outs,
-                                 max_iters);
-}
-
-int64_t dq_hip_quant_region_windows(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
-                                    uint32_t block, uint32_t expand, const uint8_t* mask, const uint32_t* area,
-                                    uint32_t min_area, uint32_t* offsets, uint32_t cap, uint32_t* coords,
-                                    uint32_t* index, const uint32_t* pixels, uint32_t* colors, uint32_t k,
-                                    uint32_t* out, uint32_t* cts, uint32_t* k_outs, int max_iters) {
-  if (!quant_windows_args_ok(regions, width, height, nregions, block, expand, area, offsets, cap, coords, index,
-                             pixels, colors, k, out, cts, k_outs, max_iters))
-    return -1;
-  const int device = current_device();
-  hipStream_t st = engine_for(device).stream();
-  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
-  WindowsInputs in;
-  in.upload(st, n, nregions, regions, mask, area, pixels);
-  uint32_t *d_offsets = nullptr, *d_coords = nullptr, *d_index = nullptr, *d_colors = nullptr, *d_out = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_offsets, no * 4, st));
-  if (cap && coords) DQ_HIP(hipMallocAsync((void**)&d_coords, (size_t)cap * 4, st));
-  if (cap && index) DQ_HIP(hipMallocAsync((void**)&d_index, (size_t)cap * 4, st));
-  if (cap && colors) DQ_HIP(hipMallocAsync((void**)&d_colors, (size_t)cap * 4, st));
-  if (out) DQ_HIP(hipMallocAsync((void**)&d_out, (size_t)std::max<uint32_t>(cap, 1u) * 4, st));
-  uint32_t total = 0;
-  const int64_t rc = quant_region_windows_on(device, st, in.regions, width, height, nregions, block, expand, in.mask,
-                                             in.area, min_area, d_offsets, cap, d_coords, d_index, in.pixels, d_colors,
-                                             k, d_out, cts, k_outs, max_iters);
-  if (rc >= 0) {   // (a refused call leaves the host arrays as they were)
-    DQ_HIP(hipMemcpyAsync(offsets, d_offsets, no * 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipMemcpyAsync(&total, d_offsets + nregions, 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipStreamSynchronize(st));
-    if (total > 0 && total <= cap) {
-      if (d_coords) DQ_HIP(hipMemcpyAsync(coords, d_coords, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-      if (d_index) DQ_HIP(hipMemcpyAsync(index, d_index, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-      if (d_colors) DQ_HIP(hipMemcpyAsync(colors, d_colors, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-      if (d_out) DQ_HIP(hipMemcpyAsync(out, d_out, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-      DQ_HIP(hipStreamSynchronize(st));
-    }
-  }
-  in.release(st);
-  for (void* p : {(void*)d_offsets, (void*)d_coords, (void*)d_index, (void*)d_colors, (void*)d_out})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return rc;
-}
-
-// Window tags (dq_wtags.hip): the windows stage up to the pair positions, then
-// the tag histogram of every window from its pairs.  Every argument check comes
-// before the first HIP call.
-static bool wtags_args_ok(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, uint32_t block,
-                          uint32_t expand, const uint32_t* area, const uint32_t* rows, uint32_t cap,
-                          const uint32_t* ids, const uint32_t* counts, const uint32_t* first, const uint32_t* inside,
-                          const uint32_t* best, const uint32_t* best_count, const uint32_t* offsets) {
-  // (rows stands where the windows call has its offsets: required; the entry arrays are its list arrays)
-  if (!windows_args_ok(regions, width, height, nregions, block, expand, area, rows, 0, ids, counts, nullptr, nullptr))
-    return false;
-  if (cap > 0 && !ids && !counts && !first) return false;
-  for (const void* p : {(const void*)first, (const void*)inside, (const void*)best, (const void*)best_count,
-                        (const void*)offsets})
-    if (((uintptr_t)p & 3u) != 0) return false;
-  return true;
-}
-
-// Three read-backs with a synchronisation each: P, T and Q (Q sizes the table;
-// a map with T > P is refused and -3 is decided there), M (-3; sizes the bitmap)
-// and E (do the entries fit), all before any output array is written.
-static int64_t window_tags_on(hipStream_t st, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                              uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
-                              const uint32_t* d_area, uint32_t min_area, uint32_t* d_rows, uint32_t cap,
-                              uint32_t* d_ids, uint32_t* d_counts, uint32_t* d_first, uint32_t* d_inside,
-                              uint32_t* d_best, uint32_t* d_best_count, uint32_t* d_offsets) {
-  const size_t no = (size_t)nregions + 1;
-  uint32_t *own_offsets = nullptr, *pair_ids = nullptr;
-  dq::WindowsArgs a{d_regions, width,   height,  nregions, block,   expand,  d_mask,  d_area,
-                    min_area,  nullptr, nullptr, nullptr,  nullptr, nullptr, nullptr, nullptr};
-  DQ_HIP(hipMallocAsync((void**)&a.blocks, dq::windows_blocks_bytes(width, height, block, nregions), st));
-  dq::WindowsView v = dq::windows_view(a, 0);   // (what the first part leaves: the pairs come later)
-  dq::WtagsArgs t{};
-  t.regions = d_regions, t.width = width, t.height = height, t.nregions = nregions, t.block = block;
-  t.mask = d_mask, t.nblocks = v.nblocks, t.pairbase = v.pairbase;
-  t.rows = d_rows, t.ids = d_ids, t.counts = d_counts, t.first = d_first;
-  t.inside = d_inside, t.best = d_best, t.best_count = d_best_count;
-  DQ_HIP(hipMallocAsync((void**)&t.live, dq::wtags_live_bytes(v.nblocks), st));
-  dq::launch_windows_blocks(a, st);
-  dq::launch_wtags_count(t, st);   // (the members of every block are counted by then: Q needs no pair)
-  DQ_HIP(hipGetLastError());
-  uint32_t npairs = 0, nrows = 0, total = 0, ncontribs = 0, nentries = 0;
-  DQ_HIP(hipMemcpyAsync(&npairs, dq::windows_pairs_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipMemcpyAsync(&nrows, dq::windows_rows_word(a), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipMemcpyAsync(&ncontribs, dq::wtags_contribs_word(t), 4, hipMemcpyDeviceToHost, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  int64_t rc;
-  if (npairs == 0xFFFFFFFFu || ncontribs == 0xFFFFFFFFu) {
-    rc = -3;
-  } else if (nrows > npairs) {
-    rc = -2;
-  } else {
-    DQ_HIP(hipMallocAsync((void**)&a.pairs, dq::windows_pairs_bytes(npairs, nrows), st));
-    if (npairs != 0 && nrows != 0) {
-      dq::launch_windows_count(a, npairs, nrows, st);
-      DQ_HIP(hipGetLastError());
-      DQ_HIP(hipMemcpyAsync(&total, dq::windows_total_word(a, npairs, nrows), 4, hipMemcpyDeviceToHost, st));
-      DQ_HIP(hipStreamSynchronize(st));
-    } else {
-      ncontribs = 0;   // (no pair, no contribution)
-    }
-    if (total == 0xFFFFFFFFu) {
-      rc = -3;
-    } else {
-      v = dq::windows_view(a, npairs);
-      if (ncontribs != 0) {
-        // the member ids of the pairs: the walk below turns the windows stage's into positions
-        DQ_HIP(hipMallocAsync((void**)&pair_ids, (size_t)npairs * 4, st));
-        DQ_HIP(hipMemcpyAsync(pair_ids, v.pair_word, (size_t)npairs * 4, hipMemcpyDeviceToDevice, st));
-      }
-      t.pair_id = pair_ids, t.pair_pos = v.pair_word, t.npairs = npairs, t.total = total;
-      a.offsets = d_offsets;
-      if (!a.offsets) {
-        DQ_HIP(hipMallocAsync((void**)&own_offsets, no * 4, st));
-        a.offsets = own_offsets;
-      }
-      t.offsets = a.offsets;
-      dq::launch_windows_offsets(a, npairs, nrows, total, st);
-      if (ncontribs != 0) dq::launch_windows_walk(a, npairs, nrows, st);
-      DQ_HIP(hipMallocAsync((void**)&t.table, dq::wtags_table_bytes(ncontribs, total, nregions), st));
-      dq::launch_wtags_fill(t, ncontribs, st);
-      DQ_HIP(hipGetLastError());
-      DQ_HIP(hipMemcpyAsync(&nentries, dq::wtags_entries_word(t, ncontribs), 4, hipMemcpyDeviceToHost, st));
-      DQ_HIP(hipStreamSynchronize(st));
-      rc = nentries;
-      dq::launch_wtags_rows(t, ncontribs, st);
-      if (nentries <= cap) dq::launch_wtags_entries(t, ncontribs, nentries, st);
-      DQ_HIP(hipGetLastError());
-      DQ_HIP(hipFreeAsync(t.table, st));
-    }
-    for (void* p : {(void*)pair_ids, (void*)own_offsets, (void*)a.pairs})
-      if (p) DQ_HIP(hipFreeAsync(p, st));
-  }
-  DQ_HIP(hipFreeAsync(t.live, st));
-  DQ_HIP(hipFreeAsync(a.blocks, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return rc;
-}
-
-int64_t dq_hip_window_tags_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
-                               uint32_t nregions, uint32_t block, uint32_t expand, const uint8_t* d_mask,
-                               const uint32_t* d_area, uint32_t min_area, uint32_t* d_rows, uint32_t cap,
-                               uint32_t* d_ids, uint32_t* d_counts, uint32_t* d_first, uint32_t* d_inside,
-                               uint32_t* d_best, uint32_t* d_best_count, uint32_t* d_offsets, void* stream) {
-  if (!wtags_args_ok(d_regions, width, height, nregions, block, expand, d_area, d_rows, cap, d_ids, d_counts, d_first,
-                     d_inside, d_best, d_best_count, d_offsets))
-    return -1;
-  // (no engine state is touched: calls on two streams may overlap)
-  hipStream_t st = engine_stream(device, stream);
-  return window_tags_on(st, d_regions, width, height, nregions, block, expand, d_mask, d_area, min_area, d_rows, cap,
-                        d_ids, d_counts, d_first, d_inside, d_best, d_best_count, d_offsets);
-}
-
-int64_t dq_hip_window_tags(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, uint32_t block,
-                           uint32_t expand, const uint8_t* mask, const uint32_t* area, uint32_t min_area,
-                           uint32_t* rows, uint32_t cap, uint32_t* ids, uint32_t* counts, uint32_t* first,
-                           uint32_t* inside, uint32_t* best, uint32_t* best_count, uint32_t* offsets) {
-  if (!wtags_args_ok(regions, width, height, nregions, block, expand, area, rows, cap, ids, counts, first, inside, best,
-                     best_count, offsets))
-    return -1;
-  Engine& e = engine_for(current_device());
-  hipStream_t st = e.stream();
-  const size_t n = (size_t)width * height, no = (size_t)nregions + 1;
-  WindowsInputs in;
-  in.upload(st, n, nregions, regions, mask, area, nullptr);
-  // the device twins of the host arrays given: rows | offsets, the three entry arrays, the three per region
-  uint32_t* const host[8] = {rows, offsets, ids, counts, first, inside, best, best_count};
-  const size_t words[8] = {no, no, cap, cap, cap, nregions, nregions, nregions};
-  uint32_t* dev[8] = {};
-  for (int i = 0; i < 8; ++i)
-    if (host[i] && words[i]) DQ_HIP(hipMallocAsync((void**)&dev[i], words[i] * 4, st));
-  const int64_t rc = window_tags_on(st, in.regions, width, height, nregions, block, expand, in.mask, in.area, min_area,
-                                    dev[0], cap, dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[1]);
-  if (rc >= 0) {   // (a refused map leaves the host arrays as they were)
-    for (int i = 0; i < 8; ++i) {
-      const bool entries = i >= 2 && i <= 4;
-      if (!dev[i] || (entries && (rc == 0 || rc > (int64_t)cap))) continue;
-      DQ_HIP(hipMemcpyAsync(host[i], dev[i], (entries ? (size_t)rc : words[i]) * 4, hipMemcpyDeviceToHost, st));
-    }
-    DQ_HIP(hipStreamSynchronize(st));
-  }
-  in.release(st);
-  for (uint32_t* p : dev)
-    if (p) DQ_HIP(hipFreeAsync(p, st));
-  return rc;
-}
-
-// Window votes (dq_wtags.hip).  There is no host-pointer twin: the call consumes
-// device arrays that only the device pipeline produces.
-int64_t dq_hip_window_votes_dev(int device, const uint32_t* d_regions, uint32_t n, uint32_t nregions,
-                                const uint32_t* d_offsets, const uint32_t* d_index, uint32_t total,
-                                const uint32_t* d_mapped, const uint32_t* cts, const uint32_t* k_outs, uint32_t k,
-                                uint32_t* d_votes, uint32_t* d_best, void* stream) {
-  if (!d_regions || !d_offsets || !cts || !k_outs || !d_votes || !d_best) return -1;
-  if (total > 0 && (!d_index || !d_mapped)) return -1;
-  if (n == 0 || n > 0x7FFFFFFFu || nregions == 0 || nregions > 0x7FFFFFFFu || k < 1 || k > dq::kVotesMaxK) return -1;
-  if (total == 0xFFFFFFFFu) return -1;   // (the windows call gives such an M up)
-  for (const void* p : {(const void*)d_regions, (const void*)d_offsets, (const void*)d_index, (const void*)d_mapped,
-                        (const void*)cts, (const void*)k_outs, (const void*)d_votes, (const void*)d_best})
-    if (((uintptr_t)p & 3u) != 0) return -1;
-  hipStream_t st = engine_stream(device, stream);
-  const size_t table = (size_t)nregions * k;
-  uint32_t *d_cts = nullptr, *d_kouts = nullptr;
-  dq::WvotesArgs a{d_regions, n, nregions, d_offsets, d_index, d_mapped, total, k, nullptr, nullptr, nullptr, d_votes,
-                   d_best};
-  DQ_HIP(hipMallocAsync((void**)&d_cts, table * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&d_kouts, (size_t)nregions * 4, st));
-  DQ_HIP(hipMallocAsync((void**)&a.jobs, dq::wvotes_jobs_bytes(nregions), st));
-  DQ_HIP(hipMemcpyAsync(d_cts, cts, table * 4, hipMemcpyHostToDevice, st));
-  DQ_HIP(hipMemcpyAsync(d_kouts, k_outs, (size_t)nregions * 4, hipMemcpyHostToDevice, st));
-  a.cts = d_cts, a.k_outs = d_kouts;
-  dq::launch_wvotes(a, st);
-  DQ_HIP(hipGetLastError());
-  unsigned long long misses = 0;
-  DQ_HIP(hipMemcpyAsync(&misses, dq::wvotes_misses_word(a), 8, hipMemcpyDeviceToHost, st));
-  for (void* p : {(void*)d_cts, (void*)d_kouts, (void*)a.jobs})
-    DQ_HIP(hipFreeAsync(p, st));
-  DQ_HIP(hipStreamSynchronize(st));
-  return (int64_t)misses;
-}
-
 // Synthetic frames of the benchmark configs (SURVEY 8c/8d generator) and the
 // output checksum the golden fixtures are keyed by.
 void dq_synth_xorshift(uint32_t* out, uint64_t n, uint64_t seed) {
@@ -2011,37 +831,26 @@ int dq_hip_block_hist(const uint32_t* in, uint32_t width, uint32_t height, const
   Engine& e = engine_for(dev);
   hipStream_t st = e.stream();
   const size_t n = (size_t)width * height, nb = (size_t)block_w * block_h, cap = (size_t)dim * dim;
-  uint32_t *d_mode = nullptr, *d_nd = nullptr, *d_keys = nullptr, *d_counts = nullptr;
-  DQ_HIP(hipMallocAsync((void**)&d_mode, nb * 4, st));
-  if (ndistinct) DQ_HIP(hipMallocAsync((void**)&d_nd, nb * 4, st));
+  dq::Staging s(st);
+  uint32_t* d_mode = s.alloc<uint32_t>(nb);
+  uint32_t* d_nd = s.twin(ndistinct, nb);
+  uint32_t *d_keys = s.twin(keys, nb * cap), *d_counts = s.twin(counts, nb * cap);
   if (keys) {
-    DQ_HIP(hipMallocAsync((void**)&d_keys, nb * cap * 4, st));
-    DQ_HIP(hipMallocAsync((void**)&d_counts, nb * cap * 4, st));
     DQ_HIP(hipMemsetAsync(d_keys, 0, nb * cap * 4, st));
     DQ_HIP(hipMemsetAsync(d_counts, 0, nb * cap * 4, st));
   }
-  int rc;
-  {
-    std::lock_guard<std::mutex> g(e.mutex());
-    e.stage_in(in, (uint32_t)n, st);
-    e.map(e.staged_in(), (uint32_t)n, e.staged_out(), palette, npal, st);
-    uint32_t* work = nullptr;
-    DQ_HIP(hipMallocAsync((void**)&work, dq::block_hist_scratch_words(block_w, block_h) * 4, st));
-    dq::BlockHistArgs a{e.staged_out(), width, height, block_w, block_h, d_mode, d_nd, d_keys, d_counts,
-                        work, nullptr, 0};
-    rc = dq::launch_block_hist(a, (int)dim, st);
-    DQ_HIP(hipFreeAsync(work, st));
-    if (quant) DQ_HIP(hipMemcpyAsync(quant, e.staged_out(), n * 4, hipMemcpyDeviceToHost, st));
-    DQ_HIP(hipMemcpyAsync(mode, d_mode, nb * 4, hipMemcpyDeviceToHost, st));
-    if (ndistinct) DQ_HIP(hipMemcpyAsync(ndistinct, d_nd, nb * 4, hipMemcpyDeviceToHost, st));
-    if (keys) {
-      DQ_HIP(hipMemcpyAsync(keys, d_keys, nb * cap * 4, hipMemcpyDeviceToHost, st));
-      DQ_HIP(hipMemcpyAsync(counts, d_counts, nb * cap * 4, hipMemcpyDeviceToHost, st));
-    }
-    DQ_HIP(hipStreamSynchronize(st));
-  }
-  for (uint32_t* p : {d_mode, d_nd, d_keys, d_counts})
-    if (p) DQ_HIP(hipFreeAsync(p, st));
+  std::lock_guard<std::mutex> g(e.mutex());
+  e.stage_in(in, (uint32_t)n, st);
+  e.map(e.staged_in(), (uint32_t)n, e.staged_out(), palette, npal, st);
+  uint32_t* work = s.alloc<uint32_t>(dq::block_hist_scratch_words(block_w, block_h));
+  dq::BlockHistArgs a{e.staged_out(), width, height, block_w, block_h, d_mode, d_nd, d_keys, d_counts,
+                      work, nullptr, 0};
+  const int rc = dq::launch_block_hist(a, (int)dim, st);
+  s.release(work);
+  s.download(quant, (const uint32_t*)e.staged_out(), n);
+  s.download(mode, d_mode, nb), s.download(ndistinct, d_nd, nb);
+  s.download(keys, d_keys, nb * cap), s.download(counts, d_counts, nb * cap);
+  s.sync();
   return rc;
 }
 
