@@ -17,7 +17,7 @@
 //
 // Passes (all on the caller's stream; no kernel waits for another workgroup,
 // a probe loop ends because the table is at most half full):
-//   1 count   the heads of every chunk of 1024 pixels, summed by the scan kernel
+//   1 count   the heads of every chunk of 1024 pixels, summed by dq_scan.h's top scan
 //             (the host reads the total back and sizes the table from it,
 //             never from 4 * n)
 //   2 insert  each head claims or finds its key in an open-addressing table
@@ -28,7 +28,8 @@
 //             flushes them once: a frame with few, long borders is the usual one
 //   3 flag    a head whose contact word equals its entry's first contact is
 //             the edge's first contact; their number per chunk of 1024 pixels
-//   4 scan    one workgroup: exclusive prefix sum of the chunk counts, total E
+//   4 scan    one workgroup (dq_scan.h's top scan): exclusive prefix sum of the
+//             chunk counts, total E
 //   5 emit    pass 3 again (the key is looked up again: no per-pixel flag is
 //             kept); edge id = chunk offset + rank in (p, dir) order; the
 //             owning thread writes the edge's entries for ids < edge_cap and
@@ -41,25 +42,26 @@
 #include <hip/hip_runtime.h>
 
 #include "dq_adjacency.h"
-#include "dq_regions.h"
+#include "dq_scan.h"
+#include "dq_stage.h"
+#include "dq_table.h"
 
 namespace dq {
 namespace {
 
-constexpr uint32_t kChunk = kRegionChunk;
-constexpr int kThreads = 256;
-static_assert(kChunk == 4 * kThreads, "four rounds of one pixel per thread in the pixel passes");
+using scan::block_excl_scan;
+using scan::chunks_of;
+using table::kNoKey;   // (no a < b key equals it)
+using table::mix;
 
-constexpr unsigned long long kNoKey = ~0ull;   // no a < b key equals it
 constexpr uint32_t kNoContact = 0xFFFFFFFFu;   // (the last pixel has no down-right neighbour)
-constexpr unsigned long long kNoSlot = ~0ull;
+constexpr unsigned long long kNoSlot = ~0ull;   // table::table_find's "not there"
 constexpr uint32_t kSlots = 128;               // LDS slots of the insert pass (and of the emit pass's degrees)
 // -DDQ_ADJACENCY_LDS_SLOTS=0 builds the insert pass without them (every head
 // straight to the table): the variant DESIGN.md 5a''' measures against.
 #ifndef DQ_ADJACENCY_LDS_SLOTS
 #define DQ_ADJACENCY_LDS_SLOTS 1
 #endif
-constexpr uint64_t kMinTableSlots = 1024;
 
 __device__ __forceinline__ unsigned long long edge_key(uint32_t a, uint32_t b) {
   if (a == b) return kNoKey;
@@ -94,45 +96,11 @@ __device__ __forceinline__ bool run_start(unsigned long long key, uint32_t lane)
   return lane == 0 || prev != key;
 }
 
-__device__ __forceinline__ unsigned long long mix(unsigned long long h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-
 __device__ __forceinline__ uint32_t colour_step(uint32_t p, uint32_t q) {
   const int dr = (int)((p >> 16) & 0xFFu) - (int)((q >> 16) & 0xFFu);
   const int dg = (int)((p >> 8) & 0xFFu) - (int)((q >> 8) & 0xFFu);
   const int db = (int)(p & 0xFFu) - (int)(q & 0xFFu);
   return (uint32_t)(abs(dr) + abs(dg) + abs(db));
-}
-
-// Exclusive prefix sum of v over the workgroup's threads (NW waves) and the
-// workgroup's total (as in dq_regions.hip).  Every thread of the workgroup calls it.
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  __syncthreads();   // (wsum may still be read from the previous call)
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-    const uint32_t s = wsum[w];
-    if (w < wave) off += s;
-    tot += s;
-  }
-  total = tot;
-  return off + inc - v;
 }
 
 // ---- 1 count ---------------------------------------------------------------
@@ -165,25 +133,17 @@ struct Table {
   uint32_t* first;            // starts as kNoContact
   uint32_t* border;           // starts as 0
   unsigned long long* step;   // starts as 0; nullptr: not asked for
-  unsigned long long mask;    // slots - 1
+  unsigned long long slots;   // a power of two
 };
 
-// Other workgroups (on other XCDs, behind other L2s) claim slots meanwhile:
-// every read of a key here is an agent-scope atomic.  A slot's key never
-// changes once claimed, and fewer than half the slots are ever claimed, so the
-// probe ends at the key or at a free slot this thread then claims.
+// the home slot of a key: the hash's low bits
+__device__ __forceinline__ unsigned long long home_slot(unsigned long long slots, unsigned long long key) {
+  return mix(key) & (slots - 1);
+}
+
 __device__ __forceinline__ void table_add(const Table& t, unsigned long long key, uint32_t cnt, uint32_t contact,
                                           uint32_t step) {
-  unsigned long long s = mix(key) & t.mask;
-  for (;;) {
-    unsigned long long k = __hip_atomic_load(&t.key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == kNoKey) {
-      k = atomicCAS(&t.key[s], kNoKey, key);
-      if (k == kNoKey) k = key;   // claimed
-    }
-    if (k == key) break;
-    s = (s + 1) & t.mask;
-  }
+  const unsigned long long s = table::table_claim(t.key, t.slots, home_slot(t.slots, key), key);
   atomicAdd(&t.border[s], cnt);
   atomicMin(&t.first[s], contact);
   if (t.step) atomicAdd(&t.step[s], (unsigned long long)step);
@@ -210,27 +170,18 @@ __global__ __launch_bounds__(kThreads) void adjacency_insert_kernel(const uint32
     const uint32_t px = steps && i < n ? pixels[i] : 0u;
 #pragma unroll
     for (uint32_t d = 0; d < 4; ++d) {
-      const bool start = run_start(key[d], lane);
-      const unsigned long long starts = __ballot(start);
-      const uint32_t h = 63u - (uint32_t)__clzll((long long)(starts & (~0ull >> (63u - lane))));
-      const bool tail = lane == 63 || ((starts >> (lane + 1)) & 1ull);
+      const WaveRun run = wave_run(run_start(key[d], lane));
       uint32_t sv = 0;
-      if (steps) {   // (uniform) segmented inclusive sum: <= 64 * 765
+      if (steps) {   // (uniform) the run's sum: <= 64 * 765
         if (key[d] != kNoKey) sv = colour_step(px, pixels[neighbour(i, d, W)]);
-#pragma unroll
-        for (uint32_t dd = 1; dd < 64; dd <<= 1) {
-          const uint32_t v = __shfl_up(sv, dd);
-          if (lane >= h + dd) sv += v;
-        }
+        sv = run_sum(sv, run);
       }
-      if (tail && key[d] != kNoKey) {
-        const uint32_t cnt = lane - h + 1, contact = 4u * (i - (lane - h)) + d;
+      if (run.tail && key[d] != kNoKey) {
+        const uint32_t cnt = run.length(lane), contact = 4u * (i + 1 - cnt) + d;
         const uint32_t slot = (uint32_t)(mix(key[d]) >> 57);   // (the table takes the low bits)
         static_assert(kSlots == 128, "the top 7 bits of the hash");
-        // (without the slots: ~key, neither free nor the key, sends every head to the table)
-        const unsigned long long was =
-            DQ_ADJACENCY_LDS_SLOTS ? atomicCAS(&s_key[slot], kNoKey, key[d]) : ~key[d];
-        if (was == kNoKey || was == key[d]) {   // (<= 4096 contacts a workgroup: the u32 sums hold)
+        // (without the slots every head goes to the table; <= 4096 contacts a workgroup: the u32 sums hold)
+        if (DQ_ADJACENCY_LDS_SLOTS && slot_claim(s_key, slot, kNoKey, key[d])) {
           atomicAdd(&s_border[slot], cnt);
           atomicMin(&s_first[slot], contact);
           if (steps) atomicAdd(&s_step[slot], sv);
@@ -246,19 +197,6 @@ __global__ __launch_bounds__(kThreads) void adjacency_insert_kernel(const uint32
 }
 
 // ---- 3 flag, 5 emit --------------------------------------------------------
-// The slot of a key in the finished table (plain loads: the insert kernel has
-// ended).  Every head's key is there; a free slot ends the probe all the same.
-__device__ __forceinline__ unsigned long long table_find(const unsigned long long* __restrict__ keys,
-                                                         unsigned long long mask, unsigned long long key) {
-  unsigned long long s = mix(key) & mask;
-  for (;;) {
-    const unsigned long long k = keys[s];
-    if (k == key) return s;
-    if (k == kNoKey) return kNoSlot;
-    s = (s + 1) & mask;
-  }
-}
-
 struct EdgeOut {
   uint32_t cap;
   uint32_t* edges;
@@ -272,11 +210,9 @@ struct EdgeOut {
 // is free or already the id's, else straight to global memory (an id that
 // touches thousands of others would otherwise take one global add per edge on
 // one word).  kNoId: ids are < nregions <= 2^32 - 1 where a degree is asked for.
-constexpr uint32_t kNoId = 0xFFFFFFFFu;
 __device__ __forceinline__ void degree_add(uint32_t* s_id, uint32_t* s_cnt, uint32_t* degree, uint32_t id) {
   const uint32_t slot = id % kSlots;
-  const uint32_t was = atomicCAS(&s_id[slot], kNoId, id);
-  if (was == kNoId || was == id) atomicAdd(&s_cnt[slot], 1u);
+  if (slot_claim(s_id, slot, kNoId, id)) atomicAdd(&s_cnt[slot], 1u);
   else atomicAdd(&degree[id], 1u);
 }
 
@@ -286,7 +222,7 @@ template <bool EMIT>
 __global__ __launch_bounds__(kThreads) void adjacency_first_kernel(
     const uint32_t* __restrict__ reg, uint32_t n, uint32_t W, uint32_t H, int conn8,
     const unsigned long long* __restrict__ t_key, const uint32_t* __restrict__ t_first,
-    const uint32_t* __restrict__ t_border, const unsigned long long* __restrict__ t_step, unsigned long long mask,
+    const uint32_t* __restrict__ t_border, const unsigned long long* __restrict__ t_step, unsigned long long slots,
     uint32_t* counts, EdgeOut o) {
   __shared__ uint32_t wsum[kThreads / 64];
   __shared__ uint32_t s_id[EMIT ? kSlots : 1], s_cnt[EMIT ? kSlots : 1];
@@ -310,7 +246,8 @@ __global__ __launch_bounds__(kThreads) void adjacency_first_kernel(
       const bool start = run_start(key[d], lane);
       slot[d] = kNoSlot;
       if (start && key[d] != kNoKey) {
-        const unsigned long long s = table_find(t_key, mask, key[d]);
+        // (every head's key is in the table; a free slot ends the probe all the same)
+        const unsigned long long s = table::table_find(t_key, slots, home_slot(slots, key[d]), key[d]);
         if (s != kNoSlot && t_first[s] == 4u * i + d) {
           firsts |= 1u << d;
           slot[d] = s;
@@ -358,31 +295,12 @@ __global__ __launch_bounds__(kThreads) void adjacency_first_kernel(
   }
 }
 
-// ---- scan (of the head counts after pass 1, of the edge counts as pass 4) -----
-// counts[0 .. nchunks) -> their exclusive prefix sums, counts[nchunks] = total
-// (E <= heads < 4 n <= 2^32).
-__global__ __launch_bounds__(1024) void adjacency_scan_kernel(uint32_t* counts, uint32_t nchunks) {
-  __shared__ uint32_t wsum[16];
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < nchunks; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < nchunks ? counts[i] : 0u;
-    uint32_t total;
-    const uint32_t excl = block_excl_scan<16>(v, wsum, total);
-    if (i < nchunks) counts[i] = carry + excl;
-    carry += total;
-  }
-  if (threadIdx.x == 0) counts[nchunks] = carry;
-}
-
-uint32_t chunks_of(uint32_t n) { return (n + kChunk - 1) / kChunk; }
-
 }  // namespace
 
 size_t adjacency_count_words(uint32_t width, uint32_t height) { return (size_t)chunks_of(width * height) + 1; }
 
 uint64_t adjacency_table_slots(uint32_t heads) {
-  uint64_t slots = kMinTableSlots;
+  uint64_t slots = table::kMinTableSlots;
   while (slots < 2 * (uint64_t)heads) slots <<= 1;
   return slots;
 }
@@ -398,7 +316,8 @@ const uint32_t* adjacency_heads_word(const AdjacencyArgs& a) { return adjacency_
 void launch_adjacency_count(const AdjacencyArgs& a, hipStream_t st) {
   const uint32_t W = a.width, H = a.height, n = W * H, nchunks = chunks_of(n);
   adjacency_count_kernel<<<nchunks, kThreads, 0, st>>>(a.regions, n, W, H, a.connectivity == 8 ? 1 : 0, a.counts);
-  adjacency_scan_kernel<<<1, 1024, 0, st>>>(a.counts, nchunks);
+  // (heads < 4 n <= 2^32, DQ_HIP_ADJACENCY_MAX_PIXELS: the saturating sums are the sums)
+  scan::scan_top_kernel<<<1, 1024, 0, st>>>(a.counts, nchunks);
 }
 
 void launch_adjacency_build(const AdjacencyArgs& a, uint32_t heads, hipStream_t st) {
@@ -411,7 +330,7 @@ void launch_adjacency_build(const AdjacencyArgs& a, uint32_t heads, hipStream_t 
   t.first = (uint32_t*)(t.key + slots);
   t.border = t.first + slots;
   t.step = a.step ? (unsigned long long*)(t.border + slots) : nullptr;   // (8-B aligned: 16 * slots bytes in)
-  t.mask = slots - 1;
+  t.slots = slots;
   (void)hipMemsetAsync(t.key, 0xFF, (size_t)slots * 12, st);
   (void)hipMemsetAsync(t.border, 0, (size_t)slots * (a.step ? 12 : 4), st);
   const bool out_on = a.edge_cap != 0;
@@ -423,10 +342,10 @@ void launch_adjacency_build(const AdjacencyArgs& a, uint32_t heads, hipStream_t 
             a.degree};
   adjacency_insert_kernel<<<nchunks, kThreads, 0, st>>>(a.regions, n, W, H, conn8, a.pixels, t);
   adjacency_first_kernel<false><<<nchunks, kThreads, 0, st>>>(a.regions, n, W, H, conn8, t.key, t.first, t.border,
-                                                             t.step, t.mask, a.counts, o);
-  adjacency_scan_kernel<<<1, 1024, 0, st>>>(a.counts, nchunks);
+                                                             t.step, t.slots, a.counts, o);
+  scan::scan_top_kernel<<<1, 1024, 0, st>>>(a.counts, nchunks);   // (E <= heads)
   adjacency_first_kernel<true><<<nchunks, kThreads, 0, st>>>(a.regions, n, W, H, conn8, t.key, t.first, t.border,
-                                                            t.step, t.mask, a.counts, o);
+                                                            t.step, t.slots, a.counts, o);
 }
 
 }  // namespace dq

@@ -55,11 +55,11 @@
 #include "dq_contain.h"
 #include "dq_scan.h"
 #include "dq_sort.h"
+#include "dq_stage.h"
 
 namespace dq {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kCountBlocks = 2048;   // grids that add into one word stride over their items
 
@@ -102,9 +102,6 @@ Scratch carve(void* scratch, uint32_t nregions) {
   return s;
 }
 
-__device__ __forceinline__ uint64_t global_thread() { return (uint64_t)blockIdx.x * kThreads + threadIdx.x; }
-
-uint32_t blocks_for(uint64_t items) { return (uint32_t)((items + kThreads - 1) / kThreads); }
 uint32_t bounded_blocks(uint64_t items) { return std::max(1u, std::min(blocks_for(items), kCountBlocks)); }
 
 // The workgroup's sum of v, in thread 0 (every thread calls it).
@@ -263,35 +260,11 @@ __global__ __launch_bounds__(kThreads) void size_bits_kernel(uint32_t R, const u
 // ---- children rows, subtree, enclosed --------------------------------------
 // Both run over the children part of the sequence, where the children of one
 // parent stand side by side: a wave first sums every run of equal parents among
-// its 64 entries (a segmented scan by shuffles), and the last lane of a run
-// makes the run's one atomic add.  One add per child instead took 212 us of a
+// its 64 entries (dq_stage.h's wave runs), and the last lane of a run makes the
+// run's one atomic add.  One add per child instead took 212 us of a
 // 0.92 ms call on batman.png, whose background has 20 000 children: adds to one
 // address go one after the other.
-struct RunOfParents {
-  uint32_t start;   // the first lane of this lane's run
-  bool tail;        // this lane is the last of its run
-};
-
-__device__ __forceinline__ RunOfParents run_of_parents(uint32_t key) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t before = __shfl_up(key, 1);
-  const unsigned long long heads = __ballot(lane == 0 || before != key);
-  RunOfParents run;
-  run.start = 63u - (uint32_t)__clzll(heads & ((2ull << lane) - 1ull));
-  run.tail = lane == 63u || ((heads >> (lane + 1u)) & 1ull) != 0;
-  return run;
-}
-
-template <class T>
-__device__ __forceinline__ T run_sum(T v, const RunOfParents& run) {   // (inclusive: the tail lane holds the run's sum)
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const T t = __shfl_up(v, d);
-    if (lane >= run.start + d) v += t;
-  }
-  return v;
-}
+__device__ __forceinline__ WaveRun run_of_parents(uint32_t key) { return wave_run(__shfl_up(key, 1) != key); }
 
 // Entry j of the children part and its parent, or kNone (past the end, or not
 // of this level): such lanes form runs of their own and add nothing.
@@ -309,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void contain_rows_kernel(uint32_t R, uint
                                                                Scratch s) {
   uint32_t r;
   const uint32_t p = child_at(global_thread(), R, nroots, reached, 0u, s, r);   // (every lane stays for the shuffles)
-  const RunOfParents run = run_of_parents(p);
+  const WaveRun run = run_of_parents(p);
   const uint32_t count = run_sum(1u, run);
   if (run.tail && p != kNone) atomicAdd(&s.childoff[p], count);
 }
@@ -320,7 +293,7 @@ __global__ __launch_bounds__(kThreads) void contain_fold_kernel(uint32_t R, uint
                                                                uint32_t reached, Scratch s) {
   uint32_t r;
   const uint32_t p = child_at(global_thread(), R, nroots, reached, level, s, r);
-  const RunOfParents run = run_of_parents(p);
+  const WaveRun run = run_of_parents(p);
   const uint32_t below = run_sum(p != kNone ? s.subtree[r] : 0u, run);
   const unsigned long long inside = run_sum(p != kNone ? s.enclosed[r] : 0ull, run);
   if (run.tail && p != kNone) {

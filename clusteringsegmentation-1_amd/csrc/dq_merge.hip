@@ -39,7 +39,8 @@
 // they are a few links long, and the 2047-link chain of the test is one thread.
 //
 // Finish: a bitmap of n bits with the first pixels of the live roots set, the
-// set bits per 1024-bit chunk, one workgroup's exclusive scan of those, and
+// set bits per 1024-bit chunk, one workgroup's exclusive scan of those
+// (dq_scan.h's top scan), and
 // the new id of a root = its chunk's offset + the set bits below its own in
 // the chunk (work over regions and n / 32 words; a pixel pass that counts
 // first[comp[reg[p]]] == p would read the whole map once more).  Then
@@ -51,16 +52,18 @@
 #include <algorithm>
 
 #include "dq_merge.h"
+#include "dq_scan.h"
+#include "dq_stage.h"
 
 namespace dq {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kChunk = 1024;                 // bits of the bitmap per count
-constexpr uint32_t kChunkWords = kChunk / 32;
+using scan::chunks_of;   // (of the bitmap: scan::kChunk bits per count)
+
+constexpr uint32_t kChunkWords = scan::kChunk / 32;
+static_assert(kChunkWords == 32, "a count per half wave of bitmap words; chunk = first pixel >> 10");
 constexpr unsigned long long kNoBest = ~0ull;     // no key equals it: d <= 195840
 constexpr unsigned long long kRestless = 1ull << 63;
-constexpr uint32_t kNoId = 0xFFFFFFFFu;           // ids are < R <= 2^31 - 1
 constexpr uint32_t kSlots = 128;                  // LDS slots of the fold pass
 // -DDQ_MERGE_LDS_SLOTS=0 builds the fold pass without them (every non-root
 // straight to global memory): the variant DESIGN.md 5a'''' measures against.
@@ -84,8 +87,6 @@ struct Scratch {
   uint32_t* links;
 };
 
-uint32_t chunks_of(uint32_t n) { return (n + kChunk - 1) / kChunk; }
-
 Scratch carve(const MergeArgs& a) {
   const size_t R = a.nregions, nchunks = chunks_of(a.n);
   Scratch s;
@@ -107,8 +108,6 @@ Scratch carve(const MergeArgs& a) {
   s.links = s.counts + nchunks + 1;
   return s;
 }
-
-__device__ __forceinline__ uint64_t global_thread() { return (uint64_t)blockIdx.x * kThreads + threadIdx.x; }
 
 // ---- init ------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void merge_init_kernel(uint32_t R, const uint32_t* __restrict__ area,
@@ -239,12 +238,8 @@ __global__ __launch_bounds__(kThreads) void merge_fold_kernel(uint32_t R, Scratc
         for (uint32_t c = 0; c < 4; ++c) bb[c] = s.bbox[4 * r + c];
       }
       const uint32_t slot = root % kSlots;
-      bool mine = false;
-      if (DQ_MERGE_LDS_SLOTS) {
-        const uint32_t was = atomicCAS(&s_root[slot], kNoId, root);
-        mine = was == kNoId || was == root;
-      }
-      if (mine) {   // (the areas of a frame sum to n < 2^31: the u32 sum holds)
+      // (the areas of a frame sum to n < 2^31: the u32 sum holds)
+      if (DQ_MERGE_LDS_SLOTS && slot_claim(s_root, slot, kNoId, root)) {
         atomicAdd(&s_area[slot], area);
         atomicMin(&s_first[slot], first);
         atomicAdd(&s_sums[3 * slot], s0);
@@ -306,37 +301,6 @@ __global__ __launch_bounds__(kThreads) void merge_count_kernel(uint32_t nwords, 
 #pragma unroll
   for (uint32_t d = 16; d >= 1; d >>= 1) c += __shfl_xor(c, d);
   if ((threadIdx.x & 31u) == 0 && w < nwords) counts[w >> 5] = c;
-}
-
-// counts[0 .. nchunks) -> their exclusive prefix sums, counts[nchunks] = R'
-// (one workgroup, as in dq_adjacency.hip).
-__global__ __launch_bounds__(1024) void merge_scan_kernel(uint32_t* counts, uint32_t nchunks) {
-  __shared__ uint32_t wsum[16];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < nchunks; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < nchunks ? counts[i] : 0u;
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(inc, d);
-      if (lane >= d) inc += t;
-    }
-    __syncthreads();   // (wsum may still be read from the round before)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t off = 0, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 16; ++w) {
-      const uint32_t t = wsum[w];
-      if (w < wave) off += t;
-      total += t;
-    }
-    if (i < nchunks) counts[i] = carry + off + inc - v;
-    carry += total;
-  }
-  if (threadIdx.x == 0) counts[nchunks] = carry;
 }
 
 struct StatsOut {
@@ -401,8 +365,6 @@ __global__ __launch_bounds__(kThreads) void merge_pixels_kernel(const uint32_t* 
   }
 }
 
-uint32_t blocks_for(uint64_t items) { return (uint32_t)((items + kThreads - 1) / kThreads); }
-
 }  // namespace
 
 size_t merge_scratch_bytes(uint32_t n, uint32_t nregions, bool with_bbox, bool with_remap) {
@@ -439,7 +401,8 @@ hipError_t launch_merge_finish(const MergeArgs& a, hipStream_t st) {
   if (filled != hipSuccess) return filled;   // (no bitmap, no numbering: nothing more is launched)
   merge_bits_kernel<<<blocks_for(R), kThreads, 0, st>>>(R, n, s);
   merge_count_kernel<<<blocks_for(nwords), kThreads, 0, st>>>(nwords, s.bitmap, s.counts);
-  merge_scan_kernel<<<1, 1024, 0, st>>>(s.counts, nchunks);
+  // counts[nchunks] = R' (merged regions <= n <= 2^31 - 1: the saturating sums are the sums)
+  scan::scan_top_kernel<<<1, 1024, 0, st>>>(s.counts, nchunks);
   const bool out_on = a.stats_cap != 0;
   StatsOut o{a.stats_cap, out_on ? a.out_area : nullptr, out_on && a.bbox ? a.out_bbox : nullptr,
              out_on ? a.out_first : nullptr, out_on ? a.out_sums : nullptr};

@@ -39,6 +39,12 @@ void launch_pixels_rows(const PixelsArgs& a, hipStream_t stream);
 void launch_pixels_lists(const PixelsArgs& a, uint32_t total, hipStream_t stream);
 const uint32_t* pixels_total_word(const PixelsArgs& a);
 
+// offsets[r] = table[rowbase[r]] for r < nregions with rowbase[r] < nrows, else `total`
+// (nregions + 1 offsets): the offsets of this stage's lists and of the capture windows'
+// (dq_windows.hip), whose tables have the same shape.
+void launch_list_offsets(uint32_t nregions, uint32_t nrows, uint32_t total, const uint32_t* rowbase,
+                         const uint32_t* table, uint32_t* offsets, hipStream_t stream);
+
 // frame[(c >> 16) * width + (c & 0xFFFF)] = values[i] for the n Coord words c.
 void launch_scatter_coords(const uint32_t* values, const uint32_t* coords, uint32_t n, uint32_t width,
                            uint32_t* frame, hipStream_t stream);

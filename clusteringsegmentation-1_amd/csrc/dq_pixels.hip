@@ -46,21 +46,15 @@
 #include <hip/hip_runtime.h>
 
 #include "dq_pixels.h"
-#include "dq_regions.h"
 #include "dq_scan.h"
+#include "dq_stage.h"
 
 namespace dq {
 namespace {
 
-constexpr uint32_t kChunk = scan::kChunk;
-constexpr int kThreads = scan::kThreads;
-static_assert(kChunk == 4 * kThreads, "four rounds of one pixel per thread in the flat passes");
 constexpr uint32_t kRowsPerBlock = kThreads / 64;   // the walk: one wave per row
 constexpr uint32_t kRowSlots = 128;                 // the rows pass: LDS slots per workgroup
-constexpr uint32_t kWalkSlotBits = 9;               // the walk: 512 LDS slots per wave (64 ids: ~4 share a slot)
-constexpr uint32_t kWalkSlots = 1u << kWalkSlotBits;
 
-constexpr uint32_t kNoId = 0xFFFFFFFFu;    // R <= 2^31 - 1: never a valid id
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;   // y0 of an id without a pixel
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;  // T <= n <= 2^31 - 1: never a table entry
 
@@ -106,8 +100,7 @@ __global__ __launch_bounds__(kThreads) void pixels_rows_kernel(const uint32_t* _
     const bool lo = top && (head || !ptop), hi = bot && (head || !pbot);
     if (lo || hi) {
       const uint32_t slot = id % kRowSlots;
-      const uint32_t was = atomicCAS(&s_id[slot], kNoId, id);
-      if (was == kNoId || was == id) {
+      if (slot_claim(s_id, slot, kNoId, id)) {
         if (lo) atomicMin(&s_lo[slot], y);
         if (hi) atomicMax(&s_hi[slot], y);
       } else {
@@ -136,27 +129,25 @@ __global__ __launch_bounds__(kThreads) void pixels_count_kernel(const uint32_t* 
     const uint32_t id = in ? reg[i] : kNoId;
     const uint32_t y = in ? i / W : 0u, x = in ? i - y * W : 0u;
     const uint32_t prev = __shfl_up(id, 1);
-    const bool head = lane == 0 || prev != id || x == 0;
-    const unsigned long long starts = __ballot(head);
-    const uint32_t h = 63u - (uint32_t)__clzll((long long)(starts & (~0ull >> (63u - lane))));
-    const bool tail = lane == 63 || ((starts >> (lane + 1)) & 1ull);
-    if (tail && id < R) {
+    const WaveRun run = wave_run(prev != id || x == 0);
+    if (run.tail && id < R) {
       const uint32_t slot = rowbase[id] + (y - y0[id]);
-      if (slot < T) atomicAdd(&table[slot], lane - h + 1);
+      if (slot < T) atomicAdd(&table[slot], run.length(lane));
     }
   }
 }
 
 // ---- 4 offsets ---------------------------------------------------------------
-// An id without a pixel has the rowbase of the next id present (or T): its
-// offset is that id's (or n), the pixels with a lower id.
-__global__ __launch_bounds__(kThreads) void pixels_offsets_kernel(uint32_t R, uint32_t T, uint32_t n,
-                                                                 const uint32_t* __restrict__ rowbase,
-                                                                 const uint32_t* __restrict__ table,
-                                                                 uint32_t* __restrict__ offsets) {
+// offsets[r] = table[rowbase[r]].  An id without a list has the rowbase of the
+// next id with one (or T): its offset is that id's (or `total`, the pixels with
+// a lower id, which is also offsets[R]).
+__global__ __launch_bounds__(kThreads) void list_offsets_kernel(uint32_t R, uint32_t T, uint32_t total,
+                                                               const uint32_t* __restrict__ rowbase,
+                                                               const uint32_t* __restrict__ table,
+                                                               uint32_t* __restrict__ offsets) {
   const uint32_t r = blockIdx.x * kThreads + threadIdx.x;
   if (r > R) return;
-  uint32_t o = n;
+  uint32_t o = total;
   if (r < R) {
     const uint32_t b = rowbase[r];
     if (b < T) o = table[b];
@@ -195,32 +186,16 @@ __global__ __launch_bounds__(kThreads) void pixels_walk_kernel(const uint32_t* _
     const uint32_t x = x0 + lane, p = base + x;
     const bool valid = slot < T;
     const uint32_t px = (valid && colors) ? pixels[p] : 0u;
-    // Groups of equal ids.  A lane first claims the wave's LDS slot of its id: the lane that finds the
-    // slot free and is in no round below is alone with its id (any other lane of that id finds the
-    // slot taken and asks for a round); a lane that finds it taken, by its id or by another, asks for
-    // a round, and a round settles every lane of its id.  Which lane claims does not matter: rank,
-    // size and leader come from the ballots.  One round per id asked for: 1 to 3 on a smooth map,
-    // a few (the slot collisions) instead of 64 on a map of specks.
+    // Groups of equal ids (dq_stage.h): rank, size and leader come from the round's ballot; a lane
+    // in no round is alone with its id.
     uint32_t rank = 0, size = 1, leader = lane;
-    const uint32_t s = (id * 2654435761u) >> (32 - kWalkSlotBits);
-    bool ask = false;
-    if (valid) ask = atomicCAS(&slots[s], kNoId, id) != kNoId;
-    unsigned long long todo = __ballot(ask);
-    __builtin_amdgcn_wave_barrier();
-    if (valid) slots[s] = kNoId;   // (free again for the next chunk)
-    __builtin_amdgcn_wave_barrier();
-    while (todo) {   // (uniform: every round takes at least the lane it reads the id of)
-      const int l = __ffsll((unsigned long long)todo) - 1;
-      const uint32_t key = __shfl(id, l);
-      const bool mine = valid && id == key;
-      const unsigned long long m = __ballot(mine);
+    wave_id_groups(slots, id, valid, [&](bool mine, unsigned long long group, int l) {
       if (mine) {
-        rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        size = (uint32_t)__popcll(m);
+        rank = (uint32_t)__popcll(group & ((1ull << lane) - 1ull));
+        size = (uint32_t)__popcll(group);
         leader = (uint32_t)l;
       }
-      todo &= ~m;
-    }
+    });
     uint32_t old = 0;
     if (valid && leader == lane) old = atomicAdd(&table[slot], size);
     old = __shfl(old, (int)leader);
@@ -278,10 +253,15 @@ void launch_pixels_lists(const PixelsArgs& a, uint32_t T, hipStream_t st) {
     pixels_count_kernel<<<chunks_of(n), kThreads, 0, st>>>(a.regions, n, W, R, T, y0, rowbase, table);
     scan::launch(scan::Words{table}, table, T, table + T, st);
   }
-  pixels_offsets_kernel<<<R / kThreads + 1, kThreads, 0, st>>>(R, T, n, rowbase, table, a.offsets);
+  launch_list_offsets(R, T, n, rowbase, table, a.offsets, st);
   if (T != 0 && (a.index || a.coords || a.colors))
     pixels_walk_kernel<<<(H + kRowsPerBlock - 1) / kRowsPerBlock, kThreads, 0, st>>>(
         a.regions, W, H, R, T, n, y0, rowbase, table, a.pixels, a.index, a.coords, a.colors);
+}
+
+void launch_list_offsets(uint32_t R, uint32_t T, uint32_t total, const uint32_t* rowbase, const uint32_t* table,
+                         uint32_t* offsets, hipStream_t st) {
+  list_offsets_kernel<<<R / kThreads + 1, kThreads, 0, st>>>(R, T, total, rowbase, table, offsets);
 }
 
 void launch_scatter_coords(const uint32_t* values, const uint32_t* coords, uint32_t n, uint32_t width, uint32_t* frame,

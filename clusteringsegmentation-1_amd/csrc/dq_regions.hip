@@ -17,7 +17,8 @@
 //              larger root's parent to the smaller, retry on a lost race).
 //   3 flatten  parent[i] = root of i; counts the roots (parent[i] == i) of
 //              every chunk of kRegionChunk pixels.
-//   4 scan     one workgroup: exclusive prefix sum of the chunk counts, total.
+//   4 scan     one workgroup (dq_scan.h's top scan): exclusive prefix sum of
+//              the chunk counts, total.
 //   5 number   roots get region id = chunk offset + rank in the chunk (raster
 //              order); a root with id < stats_cap initialises its stats.
 //   6 assign   regions[i] = regions[parent[i]]; area / bounding box / colour
@@ -31,15 +32,17 @@
 #include <hip/hip_runtime.h>
 
 #include "dq_regions.h"
+#include "dq_scan.h"
+#include "dq_stage.h"
 
 namespace dq {
 namespace {
 
+using scan::block_excl_scan;
+using scan::chunks_of;
+
 constexpr uint32_t T = kRegionTile;
-constexpr uint32_t kChunk = kRegionChunk;
-constexpr int kThreads = 256;
 static_assert(T == 64, "one wave lane per tile column");
-static_assert(kChunk == 4 * kThreads, "four pixels per thread in the linear passes");
 
 template <int LB> struct LabelOf;
 template <> struct LabelOf<1> { using type = uint8_t; };
@@ -139,12 +142,8 @@ __global__ __launch_bounds__(kThreads) void region_tile_kernel(const void* __res
   for (uint32_t y = wave; y < rows; y += kWaves) {
     const bool valid = lane < cols;
     const uint32_t L = valid ? lab[y * T + lane] : 0u;
-    const bool start = valid && (lane == 0 || lab[y * T + lane - 1] != L);
-    const unsigned long long starts = __ballot(start);
-    if (valid) {
-      const uint32_t h = 63u - (uint32_t)__clzll((long long)(starts & (~0ull >> (63u - lane))));
-      par[y * T + lane] = y * T + h;
-    }
+    const WaveRun run = wave_run(valid && (lane == 0 || lab[y * T + lane - 1] != L));
+    if (valid) par[y * T + lane] = y * T + run.start;
   }
   __syncthreads();
 
@@ -252,31 +251,6 @@ __global__ __launch_bounds__(kThreads) void region_seam_kernel(const void* __res
 }
 
 // ---- linear passes --------------------------------------------------------
-// Exclusive prefix sum of v over the workgroup's threads (NW waves) and the
-// workgroup's total.  Every thread of the workgroup calls it.
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(inc, d);
-    if (lane >= d) inc += t;
-  }
-  __syncthreads();   // (wsum may still be read from the previous call)
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t off = 0, tot = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < (uint32_t)NW; ++w) {
-    const uint32_t s = wsum[w];
-    if (w < wave) off += s;
-    tot += s;
-  }
-  total = tot;
-  return off + inc - v;
-}
-
 // The four parents of pixels base .. base + 3 (0xFFFFFFFF past n: never a root
 // flag, since i < n there is never 0xFFFFFFFF).
 __device__ __forceinline__ void load4(const uint32_t* parent, uint32_t base, uint32_t n, uint32_t p[4]) {
@@ -321,21 +295,6 @@ __global__ __launch_bounds__(kThreads) void region_flatten_kernel(uint32_t* pare
   uint32_t total;
   block_excl_scan<kThreads / 64>(c, wsum, total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
-}
-
-// counts[0 .. nchunks) -> their exclusive prefix sums, counts[nchunks] = total.
-__global__ __launch_bounds__(1024) void region_scan_kernel(uint32_t* counts, uint32_t nchunks) {
-  __shared__ uint32_t wsum[16];
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < nchunks; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
-    const uint32_t v = i < nchunks ? counts[i] : 0u;
-    uint32_t total;
-    const uint32_t excl = block_excl_scan<16>(v, wsum, total);
-    if (i < nchunks) counts[i] = carry + excl;
-    carry += total;
-  }
-  if (threadIdx.x == 0) counts[nchunks] = carry;
 }
 
 // Roots get their region id; a root with id < cap starts its region's stats.
@@ -435,32 +394,20 @@ __global__ __launch_bounds__(kThreads) void region_assign_kernel(
     }
     if (!stats) continue;
     const uint32_t prev = __shfl_up(id, 1);
-    const bool head = lane == 0 || prev != id || !valid;
-    const unsigned long long heads = __ballot(head);
-    const uint32_t h = 63u - (uint32_t)__clzll((long long)(heads & (~0ull >> (63u - lane))));
-    const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+    const WaveRun run = wave_run(prev != id || !valid);
     uint32_t rg = 0, b = 0;
-    if (sums) {   // (uniform) segmented inclusive sums of R | G << 16 and of B: <= 64 * 255 each
+    if (sums) {   // (uniform) the run's sums of R | G << 16 and of B: <= 64 * 255 each
       const uint32_t px = valid ? pixels[i] : 0u;
-      rg = ((px >> 16) & 0xFFu) | (((px >> 8) & 0xFFu) << 16);
-      b = px & 0xFFu;
-#pragma unroll
-      for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t t1 = __shfl_up(rg, d), t2 = __shfl_up(b, d);
-        if (lane >= h + d) {
-          rg += t1;
-          b += t2;
-        }
-      }
+      rg = run_sum(((px >> 16) & 0xFFu) | (((px >> 8) & 0xFFu) << 16), run);
+      b = run_sum(px & 0xFFu, run);
     }
-    if (tail && valid && id < cap) {
-      const uint32_t cnt = lane - h + 1, i0 = i - (lane - h);
+    if (run.tail && valid && id < cap) {
+      const uint32_t cnt = run.length(lane), i0 = i + 1 - cnt;
       const uint32_t ya = i0 / W, xa = i0 - ya * W, yb = i / W, xb = i - yb * W;
       // a run that wraps to the next row holds the last pixel of one row and the first of the next
       const uint32_t xlo = yb > ya ? 0u : xa, xhi = yb > ya ? W - 1 : xb;
       const uint32_t slot = id % kStatSlots;
-      const uint32_t key = atomicCAS(&s_key[slot], kNoRegion, id);
-      if (key == kNoRegion || key == id) {   // (<= 1024 pixels a workgroup: the u32 sums hold)
+      if (slot_claim(s_key, slot, kNoRegion, id)) {   // (<= 1024 pixels a workgroup: the u32 sums hold)
         atomicAdd(&s_cnt[slot], cnt);
         atomicMin(&s_xlo[slot], xlo);
         atomicMax(&s_xhi[slot], xhi);
@@ -481,7 +428,6 @@ __global__ __launch_bounds__(kThreads) void region_assign_kernel(
   }
 }
 
-uint32_t chunks_of(uint32_t n) { return (n + kChunk - 1) / kChunk; }
 size_t parent_words(uint32_t n) { return ((size_t)n + 3) & ~(size_t)3; }
 
 template <int LB>
@@ -504,7 +450,8 @@ void launch_lb(const RegionArgs& a, hipStream_t st) {
     region_seam_kernel<LB><<<(nh + nv + kThreads - 1) / kThreads, kThreads, 0, st>>>(a.labels, W, H, conn8,
                                                                                     parent, nh, nh + nv);
   region_flatten_kernel<<<nchunks, kThreads, 0, st>>>(parent, n, counts);
-  region_scan_kernel<<<1, 1024, 0, st>>>(counts, nchunks);
+  // (roots <= n <= 2^31 - 1: the saturating sums are the sums)
+  scan::scan_top_kernel<<<1, 1024, 0, st>>>(counts, nchunks);
   region_number_kernel<LB><<<nchunks, kThreads, 0, st>>>(parent, n, W, counts, a.labels, a.regions, a.stats_cap,
                                                          area, bbox, first, label, sums);
   region_assign_kernel<<<nchunks, kThreads, 0, st>>>(parent, n, W, a.regions, a.stats_cap, area, bbox, a.pixels,

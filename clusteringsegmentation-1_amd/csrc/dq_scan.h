@@ -1,21 +1,25 @@
-// dq_scan.h -- the saturating exclusive prefix sum the list stages share
-// (dq_pixels.hip, dq_windows.hip): three kernels over chunks of 1024 values
-// (sums per chunk, one workgroup over the sums, apply).  Every sum saturates at
-// 2^32 - 1 (min(sum, 2^32 - 1) is associative), so a total too large for a word
-// is seen however large it is.  Included by .hip files only.
+// dq_scan.h -- the saturating exclusive prefix sum every region-map stage
+// uses: three kernels over chunks of 1024 values (sums per chunk, one workgroup
+// over the sums, apply).  The list and graph stages (dq_pixels.hip,
+// dq_windows.hip, dq_wtags.hip, dq_contain.hip, dq_sort.h) run all three
+// through launch(); dq_regions.hip, dq_adjacency.hip and dq_merge.hip write
+// their chunk sums in a pass of their own, run scan_top_kernel over them and
+// apply the offsets in their next pass, with block_excl_scan inside the chunk.
+// Every sum saturates at 2^32 - 1 (min(sum, 2^32 - 1) is associative), so a
+// total too large for a word is seen however large it is; where the true total
+// fits a word the saturating sum is the sum.  Included by .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "dq_regions.h"
+#include "dq_stage.h"
 
 namespace dq {
 namespace scan {
 
-constexpr uint32_t kChunk = kRegionChunk;
-constexpr int kThreads = 256;
-static_assert(kChunk == 4 * kThreads, "four rounds of one value per thread");
+using dq::kChunk;     // values per entry of the top scan
+using dq::kThreads;
 
 __device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) {
   const uint32_t s = a + b;

@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "dq_stage.h"
+
 namespace dq {
 
 struct WindowsArgs {
@@ -64,5 +66,31 @@ struct WindowsView {
 WindowsView windows_view(const WindowsArgs& a, uint32_t npairs);
 // The first half of launch_windows_lists alone (after launch_windows_offsets; once per call).
 void launch_windows_walk(const WindowsArgs& a, uint32_t npairs, uint32_t nrows, hipStream_t stream);
+
+// The d x d block grid of a frame, for the kernels of both stages: BW x BH = NB blocks of dd pixels.
+struct Grid {
+  uint32_t W, H, d, dd, BW, BH, NB;
+};
+
+inline Grid block_grid(uint32_t width, uint32_t height, uint32_t block) {
+  Grid g;
+  g.W = width, g.H = height, g.d = block, g.dd = block * block;
+  g.BW = (g.W + g.d - 1) / g.d, g.BH = (g.H + g.d - 1) / g.d, g.NB = g.BW * g.BH;
+  return g;
+}
+
+// The lane's pixel of block b: its id (kNoId outside the block or the frame, or
+// for an id >= R) and whether it survives the mask.
+__device__ __forceinline__ void block_pixel(const uint32_t* __restrict__ reg, const uint8_t* __restrict__ mask,
+                                            const Grid& g, uint32_t R, uint32_t b, uint32_t lane, uint32_t& id,
+                                            bool& alive) {
+  const uint32_t by = b / g.BW, bx = b - by * g.BW;
+  const uint32_t x = bx * g.d + lane % g.d, y = by * g.d + lane / g.d;
+  const bool in = lane < g.dd && x < g.W && y < g.H;
+  const uint32_t p = in ? y * g.W + x : 0u;
+  id = in ? reg[p] : kNoId;
+  if (id >= R) id = kNoId;
+  alive = in && !(mask && mask[p] != 0);
+}
 
 }  // namespace dq

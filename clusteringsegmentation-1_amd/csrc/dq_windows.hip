@@ -50,7 +50,9 @@
 // are pixels of the frame like any other.  No floating point anywhere.
 #include <hip/hip_runtime.h>
 
+#include "dq_pixels.h"
 #include "dq_scan.h"
+#include "dq_stage.h"
 #include "dq_windows.h"
 
 namespace dq {
@@ -58,7 +60,6 @@ namespace {
 
 using scan::chunks_of;
 
-constexpr int kThreads = 256;
 constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint32_t kBlocksPerWave = 16;     // passes 1: consecutive blocks of a wave (its LDS slots serve 64 blocks)
 constexpr uint32_t kRowSlots = 128;         // pass 1: LDS slots per workgroup
@@ -68,23 +69,11 @@ constexpr uint32_t kMaxMembers = (2 * kMaxExpand * kMaxExpand + 2 * kMaxExpand +
 constexpr uint32_t kSetBits = 11;           // the hash set of a wave: 2048 slots for at most 1600 ids
 constexpr uint32_t kSetSlots = 1u << kSetBits;
 static_assert(kMaxMembers < kSetSlots, "the set never fills up");
-constexpr uint32_t kWalkSlotBits = 9;       // the walk: 512 LDS slots per wave
-constexpr uint32_t kWalkSlots = 1u << kWalkSlotBits;
 
-constexpr uint32_t kNoId = 0xFFFFFFFFu;    // R <= 2^31 - 1: never a valid id
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;   // the first block row of an id without a pixel
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 
-struct Grid {
-  uint32_t W, H, d, dd, BW, BH, NB;
-};
-
-Grid grid_of(const WindowsArgs& a) {
-  Grid g;
-  g.W = a.width, g.H = a.height, g.d = a.block, g.dd = a.block * a.block;
-  g.BW = (g.W + g.d - 1) / g.d, g.BH = (g.H + g.d - 1) / g.d, g.NB = g.BW * g.BH;
-  return g;
-}
+Grid grid_of(const WindowsArgs& a) { return block_grid(a.width, a.height, a.block); }
 
 // the first block row of the window of an id whose first own block row is j0
 __device__ __forceinline__ uint32_t window_lo(uint32_t j0, uint32_t e) { return j0 > e ? j0 - e : 0u; }
@@ -125,8 +114,7 @@ __global__ __launch_bounds__(kThreads) void windows_blocks_kernel(const uint32_t
       if (lane == (uint32_t)l) {
         ids[(size_t)b * g.dd + cnt] = key;
         const uint32_t slot = key % kRowSlots;
-        const uint32_t was = atomicCAS(&s_id[slot], kNoId, key);
-        if (was == kNoId || was == key) {
+        if (slot_claim(s_id, slot, kNoId, key)) {
           atomicMin(&s_lo[slot], by);
           atomicMax(&s_hi[slot], by);
         } else {
@@ -273,23 +261,6 @@ __global__ __launch_bounds__(kThreads) void windows_count_kernel(uint32_t P, uin
   if (slot < T) atomicAdd(&table[slot], m);
 }
 
-// ---- 6 offsets -----------------------------------------------------------------
-// An id without a window has the rowbase of the next id with one (or T): its
-// offset is that id's (or M).
-__global__ __launch_bounds__(kThreads) void windows_offsets_kernel(uint32_t R, uint32_t T, uint32_t M,
-                                                                  const uint32_t* __restrict__ rowbase,
-                                                                  const uint32_t* __restrict__ table,
-                                                                  uint32_t* __restrict__ offsets) {
-  const uint32_t r = blockIdx.x * kThreads + threadIdx.x;
-  if (r > R) return;
-  uint32_t o = M;
-  if (r < R) {
-    const uint32_t b = rowbase[r];
-    if (b < T) o = table[b];
-  }
-  offsets[r] = o;
-}
-
 // ---- 7 walk --------------------------------------------------------------------
 // pair_id[i] becomes the position of pair i.
 __global__ __launch_bounds__(kThreads) void windows_walk_kernel(Grid g, uint32_t e, uint32_t R, uint32_t P, uint32_t T,
@@ -321,24 +292,11 @@ __global__ __launch_bounds__(kThreads) void windows_walk_kernel(Grid g, uint32_t
       }
     }
     const bool valid = slot < T;
-    // Groups of equal ids, found as in the pixel lists' walk: a lane claims the wave's LDS slot of
-    // its id; the lane that finds it free and is in no round below is alone with its id, every
-    // other lane asks for a round, and a round settles every lane of its id.  A group's lanes are
-    // in block order (the pairs are block-major, a block holds an id once): the start of a lane
-    // is the m of the group's lower lanes, the group's size their sum.
+    // Groups of equal ids (dq_stage.h).  A group's lanes are in block order (the pairs are
+    // block-major, a block holds an id once): the start of a lane is the m of the group's lower
+    // lanes, the group's size their sum; a lane in no round is alone with its id.
     uint32_t before = 0, size = m, leader = lane;
-    const uint32_t s = (id * 2654435761u) >> (32 - kWalkSlotBits);
-    bool ask = false;
-    if (valid) ask = atomicCAS(&slots[s], kNoId, id) != kNoId;
-    unsigned long long todo = __ballot(ask);
-    __builtin_amdgcn_wave_barrier();
-    if (valid) slots[s] = kNoId;   // (free again for the next chunk)
-    __builtin_amdgcn_wave_barrier();
-    while (todo) {   // (uniform: every round takes at least the lane it reads the id of)
-      const int l = __ffsll(todo) - 1;
-      const uint32_t key = __shfl(id, l);
-      const bool mine = valid && id == key;
-      const unsigned long long group = __ballot(mine);
+    wave_id_groups(slots, id, valid, [&](bool mine, unsigned long long group, int) {
       uint32_t inc = mine ? m : 0u;   // inclusive prefix sums of the group's m over the wave
 #pragma unroll
       for (uint32_t d = 1; d < 64; d <<= 1) {
@@ -351,8 +309,7 @@ __global__ __launch_bounds__(kThreads) void windows_walk_kernel(Grid g, uint32_t
         size = sum;
         leader = (uint32_t)(__ffsll(group) - 1);
       }
-      todo &= ~group;
-    }
+    });
     uint32_t old = 0;
     if (valid && leader == lane) old = atomicAdd(&table[slot], size);
     old = __shfl(old, (int)leader);
@@ -480,8 +437,7 @@ void launch_windows_count(const WindowsArgs& a, uint32_t P, uint32_t T, hipStrea
 void launch_windows_offsets(const WindowsArgs& a, uint32_t P, uint32_t T, uint32_t M, hipStream_t st) {
   const BlocksLayout l = blocks_layout(grid_of(a), a.nregions);
   const uint32_t R = a.nregions;
-  windows_offsets_kernel<<<R / kThreads + 1, kThreads, 0, st>>>(R, P ? T : 0u, M, a.blocks + l.y1,
-                                                               a.pairs + (size_t)P * 2, a.offsets);
+  launch_list_offsets(R, P ? T : 0u, M, a.blocks + l.y1, a.pairs + (size_t)P * 2, a.offsets, st);   // 6 offsets
 }
 
 WindowsView windows_view(const WindowsArgs& a, uint32_t P) {

@@ -53,56 +53,25 @@
 #include <algorithm>
 
 #include "dq_scan.h"
+#include "dq_stage.h"
+#include "dq_table.h"
+#include "dq_windows.h"
 #include "dq_wtags.h"
 
 namespace dq {
 namespace {
 
 using scan::chunks_of;
+using table::kNoKey;
+using table::mix;
 
-constexpr int kThreads = 256;
 constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint32_t kBlocksPerWave = 8;      // passes 1, 2: consecutive blocks of a wave
 constexpr uint32_t kSlots = 128;            // pass 2: LDS slots per workgroup
-constexpr uint32_t kNoId = 0xFFFFFFFFu;    // R <= 2^31 - 1: never a valid id
 constexpr uint32_t kNoPos = 0xFFFFFFFFu;   // M <= 2^32 - 2: never a list position
-constexpr unsigned long long kNoKey = ~0ull;
-constexpr uint64_t kMinTableSlots = 1024;   // (an empty call's table stays a table)
 
-struct Grid {
-  uint32_t W, H, d, dd, BW, NB;
-};
-
-Grid grid_of(const WtagsArgs& a) {
-  Grid g;
-  g.W = a.width, g.H = a.height, g.d = a.block, g.dd = a.block * a.block;
-  g.BW = (g.W + g.d - 1) / g.d;
-  g.NB = a.nblocks;
-  return g;
-}
-
-__device__ __forceinline__ unsigned long long mix(unsigned long long h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-
-// The lane's pixel of block b: its id (kNoId outside the block or the frame, or
-// for an id >= R) and whether it survives the mask.
-__device__ __forceinline__ void block_pixel(const uint32_t* __restrict__ reg, const uint8_t* __restrict__ mask,
-                                            const Grid& g, uint32_t R, uint32_t b, uint32_t lane, uint32_t& id,
-                                            bool& alive) {
-  const uint32_t by = b / g.BW, bx = b - by * g.BW;
-  const uint32_t x = bx * g.d + lane % g.d, y = by * g.d + lane / g.d;
-  const bool in = lane < g.dd && x < g.W && y < g.H;
-  const uint32_t p = in ? y * g.W + x : 0u;
-  id = in ? reg[p] : kNoId;
-  if (id >= R) id = kNoId;
-  alive = in && !(mask && mask[p] != 0);
-}
+// (nblocks is the grid's block count: the windows stage's view gave it)
+Grid grid_of(const WtagsArgs& a) { return block_grid(a.width, a.height, a.block); }
 
 // ---- 1 live --------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void wtags_live_kernel(const uint32_t* __restrict__ reg,
@@ -145,21 +114,8 @@ __device__ __forceinline__ uint32_t home_slot(const Table& t, unsigned long long
   return (uint32_t)(((mix(key) & 0xFFFFFFFFull) * t.slots) >> 32);   // (the LDS slots take the top bits)
 }
 
-// Other workgroups (on other XCDs, behind other L2s) claim slots meanwhile:
-// every read of a key here is an agent-scope atomic.  A slot's key never
-// changes once claimed, and at most half the slots are ever claimed, so the
-// probe ends at the key or at a free slot this thread then claims.
 __device__ __forceinline__ void table_add(const Table& t, unsigned long long key, uint32_t n, uint32_t pos) {
-  uint32_t s = home_slot(t, key);
-  for (;;) {
-    unsigned long long k = __hip_atomic_load(&t.key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (k == kNoKey) {
-      k = atomicCAS(&t.key[s], kNoKey, key);
-      if (k == kNoKey) k = key;   // claimed
-    }
-    if (k == key) break;
-    s = s + 1 == t.slots ? 0u : s + 1;
-  }
+  const uint32_t s = table::table_claim(t.key, t.slots, home_slot(t, key), key);
   atomicAdd(&t.count[s], n);
   atomicMin(&t.first[s], pos);
 }
@@ -221,8 +177,7 @@ __global__ __launch_bounds__(kThreads) void wtags_insert_kernel(const uint32_t* 
       const unsigned long long key = ((unsigned long long)r << 32) | s;
       const uint32_t slot = (uint32_t)(mix(key) >> 57);   // (the table takes the low half)
       static_assert(kSlots == 128, "the top 7 bits of the hash");
-      const unsigned long long was = atomicCAS(&s_key[slot], kNoKey, key);
-      if (was == kNoKey || was == key) {   // (<= 32 blocks of 64 pixels a workgroup: the u32 sum holds)
+      if (slot_claim(s_key, slot, kNoKey, key)) {   // (<= 32 blocks of 64 pixels a workgroup: the u32 sum holds)
         atomicAdd(&s_count[slot], n);
         atomicMin(&s_first[slot], pos);
       } else {
@@ -309,7 +264,7 @@ __global__ __launch_bounds__(kThreads) void wtags_emit_kernel(Table t, uint32_t 
 // Twice the contributions (so at most half the slots are ever claimed), as a 32-bit count: from
 // Q = 2^31 on the table is fuller than half, and still never full (Q <= 2^32 - 2 < slots).
 uint32_t table_slots(uint32_t Q) {
-  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2 * (uint64_t)Q, kMinTableSlots), 0xFFFFFFFFull);
+  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(2 * (uint64_t)Q, table::kMinTableSlots), 0xFFFFFFFFull);
 }
 
 uint32_t bit_words(uint32_t M) { return M / 32u + 2u; }   // (word M >> 5 exists, and one more: its rank is E)

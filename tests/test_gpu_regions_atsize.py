@@ -5,8 +5,8 @@ pixel lists, containment tree, size order).
 The stage suites check every mechanism at the smallest shape that can show it,
 and none of their maps has more than 153 600 pixels.  Three things happen only
 above that, on every frame of product size:
-  * the second block of the one-workgroup top scans (region_scan_kernel,
-    adjacency_scan_kernel, merge_scan_kernel, scan::scan_top_kernel) and the
+  * the second block of the one-workgroup top scan (scan::scan_top_kernel, in
+    every stage: over root, head, edge and bitmap counts as over rows) and the
     carry into it: more than 1024 chunks of 1024 values, so more than 2^20
     pixels, regions, rows or sort counts;
   * the second trip of the bounded grid-stride loops (contain_roots_kernel,
@@ -94,7 +94,7 @@ def _device_part(what):
 
 
 # ---------------------------------------------------------------------------
-# 1. Connected regions: region_scan_kernel's second block, 1075 chunks in flatten / number / assign.
+# 1. Connected regions: scan::scan_top_kernel's second block, 1075 chunks in flatten / number / assign.
 @pytest.mark.parametrize("name,width,connectivity", [("A", 1, 4), ("B", 4, 4), ("A", 1, 8)])
 def test_regions(gpu, name, width, connectivity):
     want_reg, want = inp.regions(name, connectivity)
@@ -116,7 +116,7 @@ def test_regions(gpu, name, width, connectivity):
 
 
 # ---------------------------------------------------------------------------
-# 2. Adjacency: both scans of adjacency_scan_kernel, the table above 2^21 slots on B.
+# 2. Adjacency: both launches of scan::scan_top_kernel, the table above 2^21 slots on B.
 @pytest.mark.parametrize("name", ["A", "B"])
 def test_adjacency(gpu, name):
     want, R = inp.graph(name), inp.count(name)
@@ -135,7 +135,7 @@ def test_adjacency(gpu, name):
 
 
 # ---------------------------------------------------------------------------
-# 3. Merge: merge_scan_kernel's second block, counts[chunk] for chunks >= 1024 in the numbering; on B (more
+# 3. Merge: scan::scan_top_kernel's second block, counts[chunk] for chunks >= 1024 in the numbering; on B (more
 # than 524 288 regions) merge_link_kernel strides.
 @functools.lru_cache(maxsize=None)
 def _merged(name, min_area):

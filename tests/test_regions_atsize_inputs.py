@@ -72,7 +72,7 @@ def tree(name):
 # ---------------------------------------------------------------------------
 def test_the_maps_have_more_than_1024_chunks():
     # kRegionChunk = 1024 pixels a chunk (regions, adjacency; merge: 1024 bits of the first-pixel bitmap),
-    # 1024 threads in region_scan_kernel, adjacency_scan_kernel and merge_scan_kernel: one block of each
+    # 1024 threads in scan::scan_top_kernel over the root, head, edge and bitmap counts: one block of each
     # top scan covers 1024 * 1024 pixels
     assert N > 1048576
     for name in LABELS:
