@@ -34,6 +34,10 @@ Capture windows of a region map (per region the pixels of the d x d blocks withi
 L1 distance e of its own blocks: one pixel in many lists) and a quant per window:
     region_windows_device, region_windows,
     quant_region_windows_device, quant_region_windows
+L1 distance of every pixel to the nearest pixel of another id, every region's
+centre (the reference's findRegionCenter rule) and core (the component of the
+region that holds the centre):
+    region_distance_device, region_distance, region_cores_device, region_cores
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -142,6 +146,13 @@ def lib():
         "dq_hip_region_containment": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, u32p, u32p], c.c_int64),
         "dq_hip_regions_by_size_dev": ([c.c_int, c.c_uint32, vp, vp, vp, vp], c.c_int),
+        "dq_hip_region_distance_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, vp, vp, vp, vp, vp,
+                                        vp, vp], c.c_int),
+        "dq_hip_region_distance": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, vp, vp, vp, vp, vp, vp], c.c_int),
+        "dq_hip_region_cores_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, c.c_int, vp, vp, vp,
+                                     vp, vp, vp], c.c_int64),
+        "dq_hip_region_cores": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, c.c_int, vp, vp, vp, vp, vp],
+                                c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -1634,6 +1645,150 @@ def regions_by_size_device(t_area, num_regions=None, want_order=True, want_rank=
     if r < 0:
         raise DivQuantError("dq_hip_regions_by_size_dev: bad arguments")
     return order, rank
+
+
+# ---------------------------------------------------------------------------
+# Distance transform, centres and cores of a region map (include/dq_hip.h,
+# "region distance"): D(p) the L1 distance to the nearest pixel of another id or
+# position outside the frame, per region dmax, bbox, the threshold (rule 0: dmax;
+# rule 1: the reference's 8-bit scale), the centre set's size and the centre;
+# the core of a region is its component that holds the centre.  Exact integers,
+# independent of scheduling.  An id >= num_regions is background.
+DISTANCE_NONE = 0xFFFFFFFF             # the centre of an id with no pixel; d_cored off the cores
+DISTANCE_OUTPUTS = ("dist", "dmax", "bbox", "thresh", "count", "centre")
+CORES_OUTPUTS = ("core", "cored", "centre", "core_area", "dist")
+
+
+def _distance_shape(width, height, num_regions, rule, connectivity=8):
+    width, height = _region_shape(width, height, connectivity)
+    nreg = int(num_regions)
+    if not 1 <= nreg <= 0xFFFFFFFF:
+        raise ValueError("num_regions %d: at least 1, a uint32" % nreg)
+    if rule not in (0, 1):
+        raise ValueError("rule is 0 (exact) or 1 (the 8-bit scale), not %r" % (rule,))
+    return width, height, nreg
+
+
+def _distance_outputs(outputs, names):
+    want = tuple(names if outputs is None else outputs)
+    for name in want:
+        if name not in names:
+            raise ValueError("no output %r: %s" % (name, ", ".join(names)))
+    if not want:
+        raise ValueError("no output is wanted")
+    return want
+
+
+def _distance_map(regions2d, num_regions):
+    """A host (H, W) map of ids as contiguous uint32, and its region count (ids at or above it: background)."""
+    reg = np.asarray(regions2d)
+    if reg.ndim != 2 or reg.size == 0:
+        raise ValueError("regions2d must be a non-empty (H, W) array")
+    if reg.dtype.kind not in "ui" or reg.dtype.itemsize > 4:
+        raise ValueError("region ids are integers of at most 4 bytes, not %s" % reg.dtype)
+    if reg.dtype.kind == "i" and reg.min() < 0:
+        raise ValueError("region ids are not negative")
+    reg = _u32(reg)
+    return reg, int(reg.max()) + 1 if num_regions is None else int(num_regions)
+
+
+def _distance_shapes(w, h, nreg):
+    """name -> (shape, numpy dtype, torch dtype name) of every output of the two calls."""
+    return {"dist": ((h, w), np.uint16, "int16"), "dmax": ((nreg,), np.uint32, "int32"),
+            "bbox": ((nreg, 4), np.uint32, "int32"), "thresh": ((nreg,), np.uint32, "int32"),
+            "count": ((nreg,), np.uint32, "int32"), "centre": ((nreg,), np.uint32, "int32"),
+            "core": ((h, w), np.uint8, "uint8"), "cored": ((h, w), np.uint32, "int32"),
+            "core_area": ((nreg,), np.uint32, "int32")}
+
+
+def _distance_tensors(want, w, h, nreg, device):
+    import torch
+    shapes = _distance_shapes(w, h, nreg)
+    return {name: torch.empty(shapes[name][0], dtype=getattr(torch, shapes[name][2]), device=f"cuda:{device}")
+            for name in want}
+
+
+def region_distance_device(t_regions, width, height, num_regions, rule=0, outputs=None, device=0, stream=None):
+    """The L1 distance transform and the centres of a device-resident width x
+    height map of region ids (contiguous, 4-byte elements; an id >= num_regions
+    is background).  outputs: the names wanted of DISTANCE_OUTPUTS (None: all).
+    Returns a dict of device tensors: "dist" (height, width) int16 storage of
+    the uint16 values, "dmax", "thresh", "count", "centre" (num_regions,) and
+    "bbox" (num_regions, 4), int32 storage of the uint32 values.  Synchronous.
+    ValueError for bad tensors, sizes or names (nothing runs)."""
+    width, height, nreg = _distance_shape(width, height, num_regions, rule)
+    _elems(t_regions, width * height, 4, "t_regions")
+    want = _distance_outputs(outputs, DISTANCE_OUTPUTS)
+    out = _distance_tensors(want, width, height, nreg, device)
+    opt = lambda name: _dptr(out[name]) if name in out else None  # noqa: E731
+    r = lib().dq_hip_region_distance_dev(device, _dptr(t_regions), width, height, nreg, rule,
+                                         *[opt(name) for name in DISTANCE_OUTPUTS], _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_region_distance_dev: bad arguments")
+    return out
+
+
+def region_distance(regions2d, num_regions=None, rule=0):
+    """The same of a host (H, W) map of ids (integers of at most 4 bytes;
+    num_regions None takes regions2d.max() + 1).  Returns a dict of numpy
+    arrays: "dist" (H, W) uint16, "dmax", "thresh", "count", "centre" (R,)
+    uint32 and "bbox" (R, 4) uint32."""
+    reg, nreg = _distance_map(regions2d, num_regions)
+    h, w = reg.shape
+    _distance_shape(w, h, nreg, rule)
+    _require_gpu()
+    shapes = _distance_shapes(w, h, nreg)
+    out = {name: np.zeros(shapes[name][0], shapes[name][1]) for name in DISTANCE_OUTPUTS}
+    r = lib().dq_hip_region_distance(_ptr(reg), w, h, nreg, rule, *[_ptr(out[name]) for name in DISTANCE_OUTPUTS])
+    if r < 0:
+        raise DivQuantError("dq_hip_region_distance: bad arguments")
+    return out
+
+
+def region_cores_device(t_regions, width, height, num_regions, rule=0, connectivity=8, outputs=None, t_cored=None,
+                        device=0, stream=None):
+    """The cores of a device-resident map: per region the component (equal ids
+    under `connectivity`) that holds its centre.  outputs: the names wanted of
+    CORES_OUTPUTS (None: all).  t_cored: where "cored" goes instead of a new
+    tensor; it may be t_regions itself (in place).  Returns (kept, out): the
+    pixels kept and a dict of device tensors -- "core" (height, width) uint8,
+    "cored" (height, width) the id or 0xFFFFFFFF, "centre", "core_area"
+    (num_regions,), "dist" (height, width) int16 storage.  Synchronous.
+    ValueError for bad tensors, sizes or names (nothing runs)."""
+    width, height, nreg = _distance_shape(width, height, num_regions, rule, connectivity)
+    _elems(t_regions, width * height, 4, "t_regions")
+    want = _distance_outputs(outputs, CORES_OUTPUTS)
+    if t_cored is not None:
+        _elems(t_cored, width * height, 4, "t_cored")
+        if "cored" not in want:
+            raise ValueError("t_cored without the output \"cored\"")
+    out = _distance_tensors([name for name in want if not (name == "cored" and t_cored is not None)], width, height,
+                            nreg, device)
+    if t_cored is not None:
+        out["cored"] = t_cored
+    opt = lambda name: _dptr(out[name]) if name in out else None  # noqa: E731
+    r = lib().dq_hip_region_cores_dev(device, _dptr(t_regions), width, height, nreg, rule, connectivity,
+                                      *[opt(name) for name in CORES_OUTPUTS], _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_region_cores_dev: bad arguments")
+    return int(r), out
+
+
+def region_cores(regions2d, num_regions=None, rule=0, connectivity=8):
+    """The same of a host (H, W) map of ids.  Returns a dict of numpy arrays
+    ("core" uint8, "cored" uint32, "dist" uint16: (H, W); "centre", "core_area":
+    (R,) uint32) and the int "kept"."""
+    reg, nreg = _distance_map(regions2d, num_regions)
+    h, w = reg.shape
+    _distance_shape(w, h, nreg, rule, connectivity)
+    _require_gpu()
+    shapes = _distance_shapes(w, h, nreg)
+    out = {name: np.zeros(shapes[name][0], shapes[name][1]) for name in CORES_OUTPUTS}
+    r = lib().dq_hip_region_cores(_ptr(reg), w, h, nreg, rule, connectivity, *[_ptr(out[name]) for name in CORES_OUTPUTS])
+    if r < 0:
+        raise DivQuantError("dq_hip_region_cores: bad arguments")
+    out["kept"] = int(r)
+    return out
 
 
 # ---------------------------------------------------------------------------

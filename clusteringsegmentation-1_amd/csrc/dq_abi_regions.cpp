@@ -1,6 +1,6 @@
 // dq_abi_regions.cpp -- the region-map pipeline of the C ABI (include/dq_hip.h):
-// regions, adjacency, merge, containment, pixel lists, capture windows, window
-// tags and votes, and the per-region / per-window quant over them.
+// regions, adjacency, merge, containment, distance and cores, pixel lists,
+// capture windows, window tags and votes, and the per-region / per-window quant over them.
 //
 // Every stage has the same shape.  Both of its entry points fill the stage's
 // argument struct of the launch layer (dq_*.h; what the call owns left NULL),
@@ -23,6 +23,7 @@
 #include "dq_abi_util.h"
 #include "dq_adjacency.h"
 #include "dq_contain.h"
+#include "dq_distance.h"
 #include "dq_merge.h"
 #include "dq_pixels.h"
 #include "dq_regions.h"
@@ -213,6 +214,76 @@ int64_t run_on(hipStream_t st, dq::ContainArgs a, const ContainOut& to, hipMemcp
   if (levels) *levels = nlevels;
   if (reached) *reached = have;
   return (int64_t)nroots;
+}
+
+// -------------------------------------------------------------------------
+// Distance transform, centres and cores of a region map (dq_distance.hip).
+// The outputs of the cores call beside the distance call's (each optional):
+struct CoresOut {
+  uint8_t* core;
+  uint32_t *cored, *core_area;
+};
+
+bool args_ok(const dq::DistanceArgs& a) {
+  if (!a.regions) return false;
+  if (a.width == 0 || a.height == 0 || a.width > 65535u || a.height > 65535u ||
+      (uint64_t)a.width * a.height > 0x7FFFFFFFull)
+    return false;
+  if (a.nregions == 0 || (a.rule != 0 && a.rule != 1)) return false;
+  return aligned({a.regions, a.dmax, a.bbox, a.thresh, a.count, a.centre}) && aligned({a.dist}, 2);
+}
+
+bool args_ok(const dq::DistanceArgs& a, const CoresOut& to, int connectivity) {
+  if (!args_ok(a) || (connectivity != 4 && connectivity != 8)) return false;
+  if (!to.core && !to.cored && !to.core_area && !a.centre && !a.dist) return false;
+  return aligned({to.cored, to.core_area});
+}
+
+bool no_output(const dq::DistanceArgs& a) { return !a.dist && !a.dmax && !a.bbox && !a.thresh && !a.count && !a.centre; }
+
+// Enqueues the distance launches on st: what the caller left NULL is scratch of `s`.
+void distance_on(Staging& s, dq::DistanceArgs& a) {
+  const size_t n = (size_t)a.width * a.height, R = a.nregions;
+  if (!a.dist) a.dist = s.alloc<uint16_t>(n);
+  if (!a.dmax) a.dmax = s.alloc<uint32_t>(R);
+  if (!a.bbox) a.bbox = s.alloc<uint32_t>(R * 4);
+  if (!a.thresh) a.thresh = s.alloc<uint32_t>(R);
+  if (!a.count) a.count = s.alloc<uint32_t>(R);
+  if (!a.centre) a.centre = s.alloc<uint32_t>(R);
+  a.scratch = s.alloc_bytes(dq::distance_scratch_bytes(a.width, a.height, a.nregions));
+  dq::launch_region_distance(a, s.stream());
+  DQ_HIP(hipGetLastError());
+}
+
+int run_on(hipStream_t st, dq::DistanceArgs a) {
+  Staging s(st);
+  distance_on(s, a);
+  s.finish();
+  return 0;
+}
+
+// The distance launches, the components of the map read as u32 labels, then
+// the cores pass; waits, returns the pixels kept.
+int64_t run_on(hipStream_t st, dq::DistanceArgs a, CoresOut to, int connectivity) {
+  Staging s(st);
+  distance_on(s, a);
+  s.release(a.scratch);
+  const size_t n = (size_t)a.width * a.height;
+  dq::RegionArgs r{};
+  r.labels = a.regions, r.label_bytes = 4, r.width = a.width, r.height = a.height, r.connectivity = connectivity;
+  r.regions = s.alloc<uint32_t>(n);
+  r.scratch = s.alloc<uint32_t>(dq::region_scratch_words(a.width, a.height));
+  dq::launch_label_regions(r, st);
+  dq::CoresArgs c{};
+  c.regions = a.regions, c.width = a.width, c.height = a.height, c.nregions = a.nregions;
+  c.component = r.regions, c.centre = a.centre, c.core = to.core, c.cored = to.cored;
+  c.core_area = to.core_area ? to.core_area : s.alloc<uint32_t>(a.nregions);
+  c.kept = s.alloc<uint32_t>(1);
+  dq::launch_region_cores(c, st);
+  uint32_t kept = 0;
+  s.fetch(&kept, c.kept);
+  s.finish();
+  return (int64_t)kept;
 }
 
 // -------------------------------------------------------------------------
@@ -701,6 +772,69 @@ int64_t dq_hip_region_containment(const uint32_t* regions, uint32_t width, uint3
   a.area = s.upload(area, nregions);
   a.edges = nedges ? s.upload(edges, (size_t)nedges * 2) : nullptr;
   return run_on(st, a, to, hipMemcpyDeviceToHost, levels, reached);
+}
+
+int dq_hip_region_distance_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                               uint32_t nregions, int rule, uint16_t* d_dist, uint32_t* d_dmax, uint32_t* d_bbox,
+                               uint32_t* d_thresh, uint32_t* d_count, uint32_t* d_centre, void* stream) {
+  dq::DistanceArgs a{};
+  a.regions = d_regions, a.width = width, a.height = height, a.nregions = nregions, a.rule = rule;
+  a.dist = d_dist, a.dmax = d_dmax, a.bbox = d_bbox, a.thresh = d_thresh, a.count = d_count, a.centre = d_centre;
+  if (!args_ok(a) || no_output(a)) return -1;
+  return run_on(engine_stream(device, stream), a);
+}
+
+int dq_hip_region_distance(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, int rule,
+                           uint16_t* dist, uint32_t* dmax, uint32_t* bbox, uint32_t* thresh, uint32_t* count,
+                           uint32_t* centre) {
+  dq::DistanceArgs h{};
+  h.regions = regions, h.width = width, h.height = height, h.nregions = nregions, h.rule = rule;
+  h.dist = dist, h.dmax = dmax, h.bbox = bbox, h.thresh = thresh, h.count = count, h.centre = centre;
+  if (!args_ok(h) || no_output(h)) return -1;
+  hipStream_t st = host_stream();
+  Staging s(st);
+  const size_t n = (size_t)width * height, R = nregions;
+  dq::DistanceArgs d = h;
+  d.regions = s.upload(regions, n);
+  d.dist = s.twin(dist, n), d.dmax = s.twin(dmax, R), d.bbox = s.twin(bbox, R * 4), d.thresh = s.twin(thresh, R);
+  d.count = s.twin(count, R), d.centre = s.twin(centre, R);
+  const int rc = run_on(st, d);
+  s.download(dist, d.dist, n), s.download(dmax, d.dmax, R), s.download(bbox, d.bbox, R * 4);
+  s.download(thresh, d.thresh, R), s.download(count, d.count, R), s.download(centre, d.centre, R);
+  s.sync();
+  return rc;
+}
+
+int64_t dq_hip_region_cores_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                uint32_t nregions, int rule, int connectivity, uint8_t* d_core, uint32_t* d_cored,
+                                uint32_t* d_centre, uint32_t* d_core_area, uint16_t* d_dist, void* stream) {
+  dq::DistanceArgs a{};
+  a.regions = d_regions, a.width = width, a.height = height, a.nregions = nregions, a.rule = rule;
+  a.dist = d_dist, a.centre = d_centre;
+  const CoresOut to{d_core, d_cored, d_core_area};
+  if (!args_ok(a, to, connectivity)) return -1;
+  return run_on(engine_stream(device, stream), a, to, connectivity);
+}
+
+int64_t dq_hip_region_cores(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions, int rule,
+                            int connectivity, uint8_t* core, uint32_t* cored, uint32_t* centre, uint32_t* core_area,
+                            uint16_t* dist) {
+  dq::DistanceArgs h{};
+  h.regions = regions, h.width = width, h.height = height, h.nregions = nregions, h.rule = rule;
+  h.dist = dist, h.centre = centre;
+  if (!args_ok(h, CoresOut{core, cored, core_area}, connectivity)) return -1;
+  hipStream_t st = host_stream();
+  Staging s(st);
+  const size_t n = (size_t)width * height, R = nregions;
+  dq::DistanceArgs d = h;
+  d.regions = s.upload(regions, n);
+  d.dist = s.twin(dist, n), d.centre = s.twin(centre, R);
+  const CoresOut to{s.twin(core, n), s.twin(cored, n), s.twin(core_area, R)};
+  const int64_t kept = run_on(st, d, to, connectivity);
+  s.download(core, to.core, n), s.download(cored, to.cored, n), s.download(core_area, to.core_area, R);
+  s.download(dist, d.dist, n), s.download(centre, d.centre, R);
+  s.sync();
+  return kept;
 }
 
 int dq_hip_regions_by_size_dev(int device, uint32_t nregions, const uint32_t* d_area, uint32_t* d_order,

@@ -784,6 +784,91 @@ int64_t dq_hip_region_containment(const uint32_t *regions, uint32_t width, uint3
 int dq_hip_regions_by_size_dev(int device, uint32_t nregions, const uint32_t *d_area,
                                uint32_t *d_order, uint32_t *d_rank, void *stream);
 
+/* ---- region distance (region map -> the L1 distance of every pixel to the
+ * nearest pixel of another id, every region's centre and its core) --------------
+ * The last live step of the reference's captureRegion
+ * (ClusteringSegmentation.cpp:2538-2679): once the votes have switched the mask
+ * pixels on it takes the Manhattan distance transform of the mask
+ * (findRegionCenter, superpixels/OpenCVUtil.cpp:204-618: Meijster's algorithm
+ * with ManhattanMetric), picks one centre among the pixels of highest distance
+ * and flood-fills 8-connected from it, switching off what the fill did not
+ * reach.  These entries do the same for ALL regions of an id map in one call,
+ * with ONE exact integer answer that does not depend on scheduling.
+ * Inputs.  d_regions: a width x height map of uint32 ids.  An id < nregions = R
+ * is a region; its pixels need not be connected.  An id >= R is background: it
+ * has distance 0, no stats, and counts as "another id" for its neighbours.
+ * Rules.
+ *   1 Distance.  For a pixel p of region r, D(p) is the smallest |dx| + |dy| to
+ *     any pixel whose id is not r, or to any position just outside the frame
+ *     (column -1 or width, row -1 or height).  So D >= 1 on every region pixel
+ *     and D <= 32768 under the argument limits: exactly what the reference
+ *     computes for one mask inside its 1-pixel black border.
+ *   2 Per region.  dmax[r] is the highest D of r; bbox[r] = (x0, y0, x1, y1),
+ *     inclusive, the layout of dq_hip_label_regions_dev's d_bbox.  An id with no
+ *     pixel has dmax = 0, count = 0, thresh = 0, centre = 0xFFFFFFFF,
+ *     core_area = 0 and bbox = (0xFFFFFFFF, 0xFFFFFFFF, 0, 0).
+ *   3 Threshold.  rule = 0 (exact): thresh[r] = dmax[r].  rule = 1 (the
+ *     reference's 8-bit scale): thresh[r] is the lowest d in 1 .. dmax with
+ *     byte(d) == byte(dmax), where byte(1) = 1 and otherwise
+ *     byte(d) = max(1, (uint8)(sqrt((double)d) / (double)radius * 255 + 0.5)),
+ *     evaluated in FP64 in exactly this order, and
+ *     radius = isqrt(((bw + 2)^2 + (bh + 2)^2) >> 2) + 1 for a bbox of bw x bh
+ *     pixels: the reference's int(round(hypot((bw+2)/2, (bh+2)/2) + 0.5) + 0.01).
+ *     byte is monotone in d.  The reference's normalize(NORM_MINMAX) plus
+ *     threshold(254) keeps exactly the pixels with byte(D) == byte(dmax).
+ *   4 Centre set.  S[r] = { p of r : D(p) >= thresh[r] }; count[r] = |S|; the
+ *     sums of x and of y over S are uint64.
+ *   5 Centre, as the Coord word x | y << 16.  If count <= 2: the leftmost pixel
+ *     of S in the last row that holds one (the reference's loop breaks out of
+ *     its inner loop only, OpenCVUtil.cpp:545-553).  Otherwise
+ *     c = (sum x / count, sum y / count) in integer division (frame coordinates
+ *     give the same c as the reference's padded ROI coordinates); if c is in S
+ *     the centre is c, else the pixel of S with the lowest dx^2 + dy^2 to c,
+ *     ties to the lowest raster index.  This equals the reference's float hypot
+ *     with strict < in raster order wherever that lowest distance is under 2048
+ *     pixels: there distinct integers dx^2 + dy^2 give distinct floats.  Beyond
+ *     2048 pixels the reference's ties hang on float rounding and can differ.
+ *   6 Core.  Take the components of equal ids under `connectivity` 4 or 8 (the
+ *     reference's flood uses 8).  core(p) = 1 iff p is a region pixel in the
+ *     component of centre[id(p)]; d_cored[p] = the id there, else 0xFFFFFFFF;
+ *     core_area[r] the number of such pixels.
+ * Outputs: every pointer may be NULL (not all of them); arrays are sized by
+ * width * height or by R, nothing behind them is written.  d_cored may be
+ * d_regions itself (in place: a pixel's id is read before its word is written,
+ * and components come from a copy); no other output may overlap the map.
+ * dq_hip_region_distance_dev returns 0, dq_hip_region_cores_dev the pixels kept
+ * (the sum of core_area); both are synchronous on return.  -1, before any device
+ * work, for: NULL d_regions; width or height 0 or above 65535; width * height
+ * above 2^31 - 1; nregions == 0; rule not 0 or 1; connectivity not 4 or 8; a
+ * pointer not naturally aligned (2 B for d_dist, 4 B for the words); every
+ * output NULL.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 2.25 B per pixel and 32 B per
+ * region, plus 2 B per pixel without d_dist and 4 to 16 B per region for each
+ * per-region output left NULL (the distance call: 11 launches, no read-back).
+ * The cores call adds 8 B per pixel (the components and their union-find) and
+ * 4 B per region without d_core_area: 19 launches, 4 bytes read back. */
+int dq_hip_region_distance_dev(int device, const uint32_t *d_regions, uint32_t width,
+                               uint32_t height, uint32_t nregions, int rule,
+                               uint16_t *d_dist /*W*H*/, uint32_t *d_dmax,
+                               uint32_t *d_bbox /*4 per region*/, uint32_t *d_thresh,
+                               uint32_t *d_count, uint32_t *d_centre, void *stream);
+int64_t dq_hip_region_cores_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                uint32_t height, uint32_t nregions, int rule, int connectivity,
+                                uint8_t *d_core /*W*H*/,
+                                uint32_t *d_cored /*W*H: id or 0xFFFFFFFF*/,
+                                uint32_t *d_centre, uint32_t *d_core_area, uint16_t *d_dist,
+                                void *stream);
+/* The same on host arrays, the current device: one upload of the map, the call
+ * above, one download of the arrays asked for.  Same returns. */
+int dq_hip_region_distance(const uint32_t *regions, uint32_t width, uint32_t height,
+                           uint32_t nregions, int rule, uint16_t *dist, uint32_t *dmax,
+                           uint32_t *bbox, uint32_t *thresh, uint32_t *count, uint32_t *centre);
+int64_t dq_hip_region_cores(const uint32_t *regions, uint32_t width, uint32_t height,
+                            uint32_t nregions, int rule, int connectivity, uint8_t *core,
+                            uint32_t *cored, uint32_t *centre, uint32_t *core_area,
+                            uint16_t *dist);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
