@@ -38,6 +38,10 @@ L1 distance of every pixel to the nearest pixel of another id, every region's
 centre (the reference's findRegionCenter rule) and core (the component of the
 region that holds the centre):
     region_distance_device, region_distance, region_cores_device, region_cores
+Skeletons of all regions of a region map (Guo-Hall thinning, the reference's
+skelReduce on every region's mask at once) with the iteration that deleted
+each pixel, the skeleton's area and the region's thickness:
+    region_skeleton_device, region_skeleton
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -153,6 +157,10 @@ def lib():
                                      vp, vp, vp], c.c_int64),
         "dq_hip_region_cores": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, c.c_int, vp, vp, vp, vp, vp],
                                 c.c_int64),
+        "dq_hip_region_skeleton_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp,
+                                        u32p, u32p, vp], c.c_int64),
+        "dq_hip_region_skeleton": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp, u32p, u32p],
+                                   c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
                                               c.c_int),
@@ -1788,6 +1796,88 @@ def region_cores(regions2d, num_regions=None, rule=0, connectivity=8):
     if r < 0:
         raise DivQuantError("dq_hip_region_cores: bad arguments")
     out["kept"] = int(r)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Skeletons of all regions of a region map (include/dq_hip.h, "region
+# skeleton"): Guo-Hall two-subiteration thinning, a pixel's neighbour counting
+# only when it has the pixel's own id, so every region thins as its own mask
+# would alone (the reference's skelReduce).  Exact bits, independent of
+# scheduling.  An id >= num_regions is background.
+SKELETON_OUTPUTS = ("skel", "skeled", "when", "skel_area", "thick")
+SKELETON_MAX_ITERS = 65535
+
+
+def _skeleton_shape(width, height, num_regions, max_iters):
+    width, height, nreg = _distance_shape(width, height, num_regions, 0)
+    max_iters = int(max_iters)
+    if not 0 <= max_iters <= SKELETON_MAX_ITERS:
+        raise ValueError("max_iters %d: 0 (until stable) .. %d" % (max_iters, SKELETON_MAX_ITERS))
+    return width, height, nreg, max_iters
+
+
+def _skeleton_shapes(w, h, nreg):
+    """name -> (shape, numpy dtype, torch dtype name) of every output of the call."""
+    return {"skel": ((h, w), np.uint8, "uint8"), "skeled": ((h, w), np.uint32, "int32"),
+            "when": ((h, w), np.uint16, "int16"), "skel_area": ((nreg,), np.uint32, "int32"),
+            "thick": ((nreg,), np.uint32, "int32")}
+
+
+def region_skeleton_device(t_regions, width, height, num_regions, max_iters=0, outputs=None, t_skeled=None, device=0,
+                           stream=None):
+    """The skeletons of all regions of a device-resident width x height map of
+    region ids (contiguous, 4-byte elements; an id >= num_regions is
+    background).  max_iters: 0 runs until nothing is deleted.  outputs: the names
+    wanted of SKELETON_OUTPUTS (None: all).  t_skeled: where "skeled" goes instead
+    of a new tensor; it may be t_regions itself (in place).  Returns (kept, out):
+    the pixels kept and a dict of device tensors -- "skel" (height, width) uint8,
+    "skeled" (height, width) the id or 0xFFFFFFFF, "when" (height, width) int16
+    storage of the uint16 iteration that deleted the pixel, "skel_area", "thick"
+    (num_regions,) -- and the ints "iterations" (the last iteration that deleted a
+    pixel) and "converged".  Synchronous.  ValueError for bad tensors, sizes or
+    names (nothing runs)."""
+    width, height, nreg, max_iters = _skeleton_shape(width, height, num_regions, max_iters)
+    _elems(t_regions, width * height, 4, "t_regions")
+    want = _distance_outputs(outputs, SKELETON_OUTPUTS)
+    if t_skeled is not None:
+        _elems(t_skeled, width * height, 4, "t_skeled")
+        if "skeled" not in want:
+            raise ValueError("t_skeled without the output \"skeled\"")
+    import torch
+    shapes = _skeleton_shapes(width, height, nreg)
+    out = {name: torch.empty(shapes[name][0], dtype=getattr(torch, shapes[name][2]), device=f"cuda:{device}")
+           for name in want if not (name == "skeled" and t_skeled is not None)}
+    if t_skeled is not None:
+        out["skeled"] = t_skeled
+    opt = lambda name: _dptr(out[name]) if name in out else None  # noqa: E731
+    iterations, converged = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    r = lib().dq_hip_region_skeleton_dev(device, _dptr(t_regions), width, height, nreg, max_iters,
+                                         *[opt(name) for name in SKELETON_OUTPUTS], ctypes.byref(iterations),
+                                         ctypes.byref(converged), _stream_ptr(stream))
+    if r < 0:
+        raise DivQuantError("dq_hip_region_skeleton_dev: bad arguments")
+    out["iterations"], out["converged"] = int(iterations.value), int(converged.value)
+    return int(r), out
+
+
+def region_skeleton(regions2d, num_regions=None, max_iters=0):
+    """The same of a host (H, W) map of ids (integers of at most 4 bytes;
+    num_regions None takes regions2d.max() + 1).  Returns a dict of numpy arrays
+    ("skel" uint8, "skeled" uint32, "when" uint16: (H, W); "skel_area", "thick":
+    (R,) uint32) and the ints "kept", "iterations" and "converged"."""
+    reg, nreg = _distance_map(regions2d, num_regions)
+    h, w = reg.shape
+    _, _, nreg, max_iters = _skeleton_shape(w, h, nreg, max_iters)
+    _require_gpu()
+    shapes = _skeleton_shapes(w, h, nreg)
+    out = {name: np.zeros(shapes[name][0], shapes[name][1]) for name in SKELETON_OUTPUTS}
+    iterations, converged = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    r = lib().dq_hip_region_skeleton(_ptr(reg), w, h, nreg, max_iters, *[_ptr(out[name]) for name in SKELETON_OUTPUTS],
+                                     ctypes.byref(iterations), ctypes.byref(converged))
+    if r < 0:
+        raise DivQuantError("dq_hip_region_skeleton: bad arguments")
+    out["kept"], out["iterations"], out["converged"] = int(r), int(iterations.value), int(converged.value)
     return out
 
 

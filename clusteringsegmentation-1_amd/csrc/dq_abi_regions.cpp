@@ -1,5 +1,5 @@
 // dq_abi_regions.cpp -- the region-map pipeline of the C ABI (include/dq_hip.h):
-// regions, adjacency, merge, containment, distance and cores, pixel lists,
+// regions, adjacency, merge, containment, distance and cores, skeletons, pixel lists,
 // capture windows, window tags and votes, and the per-region / per-window quant over them.
 //
 // Every stage has the same shape.  Both of its entry points fill the stage's
@@ -27,6 +27,7 @@
 #include "dq_merge.h"
 #include "dq_pixels.h"
 #include "dq_regions.h"
+#include "dq_skeleton.h"
 #include "dq_windows.h"
 #include "dq_wtags.h"
 
@@ -283,6 +284,59 @@ int64_t run_on(hipStream_t st, dq::DistanceArgs a, CoresOut to, int connectivity
   uint32_t kept = 0;
   s.fetch(&kept, c.kept);
   s.finish();
+  return (int64_t)kept;
+}
+
+// -------------------------------------------------------------------------
+// Skeletons of a region map (dq_skeleton.hip).
+bool args_ok(const dq::SkeletonArgs& a) {
+  if (!a.regions) return false;
+  if (a.width == 0 || a.height == 0 || a.width > 65535u || a.height > 65535u ||
+      (uint64_t)a.width * a.height > 0x7FFFFFFFull)
+    return false;
+  if (a.nregions == 0 || a.max_iters > dq::kSkeletonMaxIters) return false;
+  if (!a.skel && !a.skeled && !a.when && !a.skel_area && !a.thick) return false;
+  return aligned({a.regions, a.skeled, a.skel_area, a.thick}) && aligned({a.when}, 2);
+}
+
+// How many thinning launches go out before the next read-back: 2, 4, then 8 at a time.
+uint32_t skeleton_group(uint32_t launches) { return launches < 2 ? 2u : launches < 6 ? 4u : 8u; }
+
+// Enqueues the planes pass, the thinning launches in groups and the outputs pass
+// on st with scratch owned by the call, waits, returns the pixels kept.  The host
+// reads one word per launch of a group back (the last iteration of the launch that
+// deleted) and stops at a launch with an iteration that deleted nothing.
+int64_t run_on(hipStream_t st, dq::SkeletonArgs a, uint32_t* iterations, uint32_t* converged) {
+  Staging s(st);
+  if (a.thick && !a.when) a.when = s.alloc<uint16_t>((size_t)a.width * a.height);
+  a.scratch = s.alloc_bytes(dq::skeleton_scratch_bytes(a.width, a.height));
+  dq::launch_skeleton_planes(a, st);
+  const uint32_t limit = a.max_iters ? a.max_iters : dq::kSkeletonMaxIters;
+  uint32_t ran = 0, launches = 0, last_deleting = 0;
+  bool stable = false;
+  uint32_t last[8];
+  // An iteration that deletes nothing leaves a fixed point: the deleting iterations are 1 .. I.
+  while (ran < limit && !stable) {
+    const uint32_t from = launches, group = skeleton_group(launches);
+    for (; launches < from + group && ran < limit; ++launches) {
+      const uint32_t iters = std::min(dq::kSkeletonIters, limit - ran);
+      dq::launch_skeleton_thin(a, launches, iters, st);
+      ran += iters;
+    }
+    s.fetch(last, dq::skeleton_last_words(a) + from, launches - from);
+    s.sync();
+    for (uint32_t l = from; l < launches && !stable; ++l) {
+      const uint32_t first = l * dq::kSkeletonIters, iters = std::min(dq::kSkeletonIters, limit - first);
+      if (last[l - from]) last_deleting = first + last[l - from];
+      stable = last[l - from] < iters;
+    }
+  }
+  dq::launch_skeleton_outputs(a, launches, st);
+  uint32_t kept = 0;
+  s.fetch(&kept, dq::skeleton_kept_word(a));
+  s.finish();
+  if (iterations) *iterations = last_deleting;
+  if (converged) *converged = stable ? 1u : 0u;
   return (int64_t)kept;
 }
 
@@ -833,6 +887,38 @@ int64_t dq_hip_region_cores(const uint32_t* regions, uint32_t width, uint32_t he
   const int64_t kept = run_on(st, d, to, connectivity);
   s.download(core, to.core, n), s.download(cored, to.cored, n), s.download(core_area, to.core_area, R);
   s.download(dist, d.dist, n), s.download(centre, d.centre, R);
+  s.sync();
+  return kept;
+}
+
+int64_t dq_hip_region_skeleton_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                   uint32_t nregions, uint32_t max_iters, uint8_t* d_skel, uint32_t* d_skeled,
+                                   uint16_t* d_when, uint32_t* d_skel_area, uint32_t* d_thick, uint32_t* iterations,
+                                   uint32_t* converged, void* stream) {
+  dq::SkeletonArgs a{};
+  a.regions = d_regions, a.width = width, a.height = height, a.nregions = nregions, a.max_iters = max_iters;
+  a.skel = d_skel, a.skeled = d_skeled, a.when = d_when, a.skel_area = d_skel_area, a.thick = d_thick;
+  if (!args_ok(a)) return -1;
+  return run_on(engine_stream(device, stream), a, iterations, converged);
+}
+
+int64_t dq_hip_region_skeleton(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                               uint32_t max_iters, uint8_t* skel, uint32_t* skeled, uint16_t* when,
+                               uint32_t* skel_area, uint32_t* thick, uint32_t* iterations, uint32_t* converged) {
+  dq::SkeletonArgs h{};
+  h.regions = regions, h.width = width, h.height = height, h.nregions = nregions, h.max_iters = max_iters;
+  h.skel = skel, h.skeled = skeled, h.when = when, h.skel_area = skel_area, h.thick = thick;
+  if (!args_ok(h)) return -1;
+  hipStream_t st = host_stream();
+  Staging s(st);
+  const size_t n = (size_t)width * height, R = nregions;
+  dq::SkeletonArgs d = h;
+  d.regions = s.upload(regions, n);
+  d.skel = s.twin(skel, n), d.skeled = s.twin(skeled, n), d.when = s.twin(when, n);
+  d.skel_area = s.twin(skel_area, R), d.thick = s.twin(thick, R);
+  const int64_t kept = run_on(st, d, iterations, converged);
+  s.download(skel, d.skel, n), s.download(skeled, d.skeled, n), s.download(when, d.when, n);
+  s.download(skel_area, d.skel_area, R), s.download(thick, d.thick, R);
   s.sync();
   return kept;
 }

@@ -231,17 +231,6 @@ __global__ __launch_bounds__(kThreads) void distance_rows_kernel(const uint32_t*
 }
 
 // ---- per-region values -----------------------------------------------------
-// The highest v over the run's lanes up to this one (the tail lane holds the run's).
-__device__ __forceinline__ uint32_t run_max(uint32_t v, const WaveRun& run) {
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(v, d);
-    if (lane >= run.start + d) v = max(v, t);
-  }
-  return v;
-}
-
 // The lanes of a wave hold consecutive pixels: each run of lanes with one region
 // id adds once, from its last lane, into the workgroup's slot of the id.
 __global__ __launch_bounds__(kThreads) void distance_stats_kernel(const uint32_t* __restrict__ regions, uint32_t n,

@@ -1,6 +1,6 @@
 // dq_stage.h -- the device idioms the region-map stages share (dq_regions.hip,
 // dq_adjacency.hip, dq_merge.hip, dq_pixels.hip, dq_windows.hip, dq_wtags.hip,
-// dq_contain.hip): the workgroup and chunk sizes, runs of equal keys along a
+// dq_contain.hip, dq_distance.hip, dq_skeleton.hip): the workgroup and chunk sizes, runs of equal keys along a
 // wave, the workgroup's LDS slot cache and groups of equal ids in a wave.  Free
 // functions of a few lines each; beside it dq_scan.h (prefix sums) and
 // dq_table.h (the 64-bit hash table).
@@ -50,6 +50,17 @@ __device__ __forceinline__ T run_sum(T v, const WaveRun& run) {
   for (uint32_t d = 1; d < 64; d <<= 1) {
     const T t = __shfl_up(v, d);
     if (lane >= run.start + d) v += t;
+  }
+  return v;
+}
+
+// The highest v over the run's lanes up to this one (the tail lane holds the run's).
+__device__ __forceinline__ uint32_t run_max(uint32_t v, const WaveRun& run) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(v, d);
+    if (lane >= run.start + d) v = max(v, t);
   }
   return v;
 }

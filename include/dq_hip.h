@@ -869,6 +869,76 @@ int64_t dq_hip_region_cores(const uint32_t *regions, uint32_t width, uint32_t he
                             uint32_t *cored, uint32_t *centre, uint32_t *core_area,
                             uint16_t *dist);
 
+/* ---- region skeleton (region map -> the one-pixel-wide skeleton of every
+ * region, by Guo-Hall two-subiteration thinning) -------------------------------
+ * The live body of the reference's captureRegion, clockwiseScanForShapeBounds
+ * (ClusteringSegmentation.cpp:1276-1306), renders each visited region into a
+ * frame-sized mask and thins it (ClusteringSegmentation.cpp:6303-6321 ->
+ * skelReduce, superpixels/OpenCVUtil.cpp:1619 -> NormalizeLetter, :1548-1617 ->
+ * ThinSubiteration1 / ThinSubiteration2, :1458-1546).  This entry does the same
+ * for ALL regions of an id map in one call.  Regions are disjoint and a pixel's
+ * neighbour counts only when it has the pixel's own id, so every region gets
+ * exactly the bits the reference gets from that region's mask alone: ONE exact
+ * answer that does not depend on scheduling.
+ * Inputs.  d_regions: a width x height map of uint32 ids.  An id < nregions = R
+ * is a region; its pixels need not be connected.  An id >= R is background.
+ * max_iters: 0 runs until nothing is deleted any more.
+ * Rules.
+ *   1 Neighbours.  For a pixel p of region r: n0 = NW, n1 = N, n2 = NE, n3 = E,
+ *     n4 = SE, n5 = S, n6 = SW, n7 = W.  n_k = 1 iff that position lies in the
+ *     frame, has id r and is still alive; else 0 (the reference's mask has a
+ *     1-pixel border of zeros, and another region is not in the mask).
+ *   2 Counts.  C  = (!n1 & (n2|n3)) + (!n3 & (n4|n5)) + (!n5 & (n6|n7)) +
+ *     (!n7 & (n0|n1)); N1 = (n0|n1) + (n2|n3) + (n4|n5) + (n6|n7);
+ *     N2 = (n1|n2) + (n3|n4) + (n5|n6) + (n7|n0); N = min(N1, N2).
+ *   3 Subiteration 1 deletes every alive p with C == 1, N in {2, 3} and
+ *     ((n1 | n2 | !n4) & n3) == 0; subiteration 2 the same with
+ *     ((n5 | n6 | !n0) & n7) == 0.  A subiteration decides for all pixels from
+ *     the state before it.  (The reference writes ~ on 0/1 ints; under its & with
+ *     a 0/1 value that is the logical not.)
+ *   4 Iterations.  An iteration is subiteration 1, then subiteration 2 on its
+ *     result; iterations count from 1.  The run stops after the first iteration
+ *     that deletes nothing (converged = 1; the reference's stop rule), after
+ *     max_iters iterations when max_iters > 0, and after 65535 in any case; in the
+ *     last two cases converged = 1 only if the last iteration that ran deleted
+ *     nothing.  *iterations = the number of the last iteration that deleted a
+ *     pixel, 0 if none did.
+ *   5 Outputs.  skel[p] = 1 iff p is a region pixel still alive, else 0;
+ *     skeled[p] = the id there, else 0xFFFFFFFF; when[p] = the iteration that
+ *     deleted p, 0 for a pixel kept and for background; skel_area[r] = the alive
+ *     pixels of r; thick[r] = the highest when over r, 0 if r lost nothing.  An id
+ *     with no pixel has skel_area = 0 and thick = 0.
+ * Outputs: every array pointer may be NULL (not all five); arrays are sized by
+ * width * height or by R, nothing behind them is written.  iterations and
+ * converged are host words and may be NULL.  d_skeled may be d_regions itself
+ * (in place: the ids are read by one pass before the first thinning step, and
+ * at the end each pixel's id is read before its word is written); no other
+ * output may overlap the map.  Returns the pixels kept (the sum of skel_area),
+ * synchronous on return.  -1, before any device work, for: NULL d_regions;
+ * width or height 0 or above 65535; width * height above 2^31 - 1;
+ * nregions == 0; max_iters > 65535; a pointer not naturally aligned (2 B for
+ * d_when, 4 B for the words); every output array NULL.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 0.75 B per pixel (six bit planes,
+ * rows padded to 64 pixels), 8 B per tile of 384 x 64 pixels and 16 KB; nothing
+ * per region; plus 2 B per pixel when d_thick is given without d_when.
+ * Launches: 3 + one per 16 iterations (sent in groups of 2, 4, then 8 at a time;
+ * those past the end cost a flag test per tile); read-backs: one per group (4 B a
+ * launch) and the pixels kept. */
+int64_t dq_hip_region_skeleton_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                   uint32_t height, uint32_t nregions, uint32_t max_iters,
+                                   uint8_t *d_skel /*W*H*/,
+                                   uint32_t *d_skeled /*W*H: id or 0xFFFFFFFF*/,
+                                   uint16_t *d_when /*W*H*/, uint32_t *d_skel_area,
+                                   uint32_t *d_thick, uint32_t *iterations, uint32_t *converged,
+                                   void *stream);
+/* The same on host arrays, the current device: one upload of the map, the call
+ * above, one download of the arrays asked for.  Same returns. */
+int64_t dq_hip_region_skeleton(const uint32_t *regions, uint32_t width, uint32_t height,
+                               uint32_t nregions, uint32_t max_iters, uint8_t *skel,
+                               uint32_t *skeled, uint16_t *when, uint32_t *skel_area,
+                               uint32_t *thick, uint32_t *iterations, uint32_t *converged);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
