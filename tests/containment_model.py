@@ -14,6 +14,8 @@ Plus the map builders the tests share and a host edge list of a map.
 import numpy as np
 
 NONE = 0xFFFFFFFF
+# the tree's output arrays, in the order of the C entry point's pointers
+ARRAYS = ("depth", "parent", "roots", "child_offsets", "children", "subtree", "enclosed", "order", "pos")
 
 
 def edges_of(regions2d, connectivity=4):

@@ -1,13 +1,11 @@
 """GPU: the region adjacency graph of a region map (include/dq_hip.h, "region
 adjacency graph").
 
-The reference is the numpy model below, which never uses the code under test:
-per direction the pairs (p, q) with different ids, all contacts sorted by
-(p, q), np.unique over the keys (a << 32 | b), edges ordered by the index of
-their first contact, step by np.add.at, degree by np.bincount.  Equality is
-exact everywhere: array_equal on every array, and the edge count E.  For
-regions = arange(w * h) the model gives E = 2wh - w - h (4-connectivity) and
-4wh - 3w - 3h + 2 (8) with every border 1; those closed forms are asserted too.
+The reference is adjacency_model of adjacency_model.py, which never uses the
+code under test.  Equality is exact everywhere: array_equal on every array, and
+the edge count E.  For regions = arange(w * h) the model gives E = 2wh - w - h
+(4-connectivity) and 4wh - 3w - 3h + 2 (8) with every border 1; those closed
+forms are asserted too.  The maps are adjacency_map of region_inputs.py.
 
 The pixel passes work on chunks of 1024 pixels and a wave holds 64 consecutive
 pixels; the shapes are the smallest at which each mechanism can fail."""
@@ -19,6 +17,9 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
+from adjacency_model import adjacency_model
+from region_dev import same, to_dev, to_host
+from region_inputs import adjacency_base, frame
 
 pytestmark = pytest.mark.gpu
 
@@ -26,134 +27,24 @@ GUARD_WORD = 0xA5A5A5A5
 PER = {"edges": 2, "border": 1, "contact": 2, "step": 2}   # 4-byte words per edge
 
 
-# ---------------------------------------------------------------------------
-# The reference.
-def adjacency_model(reg2d, connectivity, pixels=None, num_regions=None):
-    """dict(E, edges, border, contact[, step][, degree]) of a 2-D id map."""
-    reg2d = np.asarray(reg2d)
-    h, w = reg2d.shape
-    r = reg2d.reshape(-1).astype(np.uint64)
-    idx = np.arange(h * w, dtype=np.int64).reshape(h, w)
-    pairs = [(idx[:, :-1], idx[:, 1:])]                         # right
-    if connectivity == 8:
-        pairs.append((idx[:-1, 1:], idx[1:, :-1]))              # down-left
-    else:
-        assert connectivity == 4
-    pairs.append((idx[:-1, :], idx[1:, :]))                     # down
-    if connectivity == 8:
-        pairs.append((idx[:-1, :-1], idx[1:, 1:]))              # down-right
-    p = np.concatenate([a.reshape(-1) for a, _ in pairs])
-    q = np.concatenate([b.reshape(-1) for _, b in pairs])
-    assert (p < q).all()
-    keep = r[p] != r[q]
-    p, q = p[keep], q[keep]
-    order = np.lexsort((q, p))
-    p, q = p[order], q[order]
-    a, b = np.minimum(r[p], r[q]), np.maximum(r[p], r[q])
-    key = (a << np.uint64(32)) | b
-    uniq, first, inverse, counts = np.unique(key, return_index=True, return_inverse=True, return_counts=True)
-    by_first = np.argsort(first, kind="stable")
-    rank = np.empty(len(uniq), np.int64)
-    rank[by_first] = np.arange(len(uniq))
-    uniq, first, counts = uniq[by_first], first[by_first], counts[by_first]
-    out = {"E": len(uniq),
-           "edges": np.stack([uniq >> np.uint64(32), uniq & np.uint64(0xFFFFFFFF)], axis=1).astype(np.uint32),
-           "border": counts.astype(np.uint32),
-           "contact": np.stack([p[first], q[first]], axis=1).astype(np.uint32)}
-    if pixels is not None:
-        px = np.asarray(pixels, np.uint32).reshape(-1)
-        d = np.zeros(len(p), np.uint64)
-        for shift in (16, 8, 0):
-            cp, cq = ((px[p] >> shift) & 0xFF).astype(np.int64), ((px[q] >> shift) & 0xFF).astype(np.int64)
-            d += np.abs(cp - cq).astype(np.uint64)
-        step = np.zeros(len(uniq), np.uint64)
-        np.add.at(step, rank[inverse.reshape(-1)], d)
-        out["step"] = step
-    if num_regions is not None:
-        out["degree"] = np.bincount(out["edges"].reshape(-1).astype(np.int64), minlength=num_regions).astype(np.uint32)
-    for v in out.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return out
-
-
-# ---------------------------------------------------------------------------
-# Maps: (h, w) arrays of uint32 ids.
-def _noise(w, h, k, seed=0):
-    return (fx.xorshift(w * h, seed=fx.SEED + seed) % np.uint32(k)).astype(np.uint32).reshape(h, w)
-
-
-def _map(name, w, h):
-    ys, xs = np.mgrid[0:h, 0:w]
-    n = w * h
-    if name == "arange":
-        return np.arange(n, dtype=np.uint32).reshape(h, w)
-    if name == "reversed":      # a > b at p < q everywhere
-        return np.arange(n, dtype=np.uint32)[::-1].reshape(h, w).copy()
-    if name == "permutation":
-        return np.argsort(fx.xorshift(n, seed=fx.SEED + 5), kind="stable").astype(np.uint32).reshape(h, w)
-    if name == "halves":
-        return (xs >= w // 2).astype(np.uint32)
-    if name == "quadrants":
-        return ((xs >= w // 2) + 2 * (ys >= h // 2)).astype(np.uint32)
-    if name == "vstripes":      # one edge, a run of right-contacts across every wave
-        return (xs & 1).astype(np.uint32)
-    if name == "k4":            # [[0, 1], [2, 3]] tiled: K4 at every corner, crossing diagonals
-        return ((xs & 1) + 2 * (ys & 1)).astype(np.uint32)
-    if name == "checker":       # 8-connectivity diagonals join equal ids: no contact
-        return ((xs + ys) & 1).astype(np.uint32)
-    if name == "constant":
-        return np.full((h, w), 7, np.uint32)
-    if name == "huge_ids":      # ids up to 0xFFFFFFFE (no degree array is possible)
-        return (_noise(w, h, 5, seed=9) + np.uint32(0xFFFFFFFA)).astype(np.uint32)
-    if name.startswith("noise"):
-        return _noise(w, h, int(name[5:]))
-    raise KeyError(name)
-
-
-@functools.lru_cache(maxsize=None)
-def _base(name, w, h):
-    a = _map(name, w, h)
-    a.setflags(write=False)
-    return a
-
-
-@functools.lru_cache(maxsize=None)
-def _frame(w, h):
-    px = fx.xorshift(w * h, seed=fx.SEED + 77)   # 0x00RRGGBB
-    px.setflags(write=False)
-    return px
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(name, w, h, connectivity):
-    """The model of a map, once (with the steps of _frame and, where the ids allow, the degree)."""
-    reg = _base(name, w, h)
+    """The model of a map, once (with the steps of frame and, where the ids allow, the degree)."""
+    reg = adjacency_base(name, w, h)
     nreg = int(reg.max()) + 1
-    return adjacency_model(reg, connectivity, _frame(w, h), nreg if nreg <= 1 << 20 else None)
-
-
-def _to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    signed = {"u4": np.int32, "u8": np.int64}[a.dtype.str[1:]]
-    return torch.from_numpy(a.view(signed).copy()).to("cuda:0")
-
-
-def _to_host(t, dtype):
-    return t.cpu().numpy().view(dtype)
+    return adjacency_model(reg, connectivity, frame(w, h), nreg if nreg <= 1 << 20 else None)
 
 
 def _unsigned(g):
-    return {k: _to_host(v, np.uint64 if k == "step" else np.uint32) for k, v in g.items()}
+    return {k: to_host(v, np.uint64 if k == "step" else np.uint32) for k, v in g.items()}
 
 
 def _run(gpu, reg2d, connectivity, cap=0, pixels=None, num_regions=0, stream=None):
     """region_adjacency_device on fresh tensors -> (E, graph as unsigned numpy)."""
     import torch
     h, w = reg2d.shape
-    t_reg = _to_dev(reg2d.reshape(-1))
-    t_px = _to_dev(pixels) if pixels is not None else None
+    t_reg = to_dev(reg2d.reshape(-1))
+    t_px = to_dev(pixels) if pixels is not None else None
     if stream is not None:   # (the tensors above were filled on the current stream)
         stream.wait_stream(torch.cuda.current_stream())
     e, g = gpu.region_adjacency_device(t_reg, w, h, connectivity=connectivity, edge_capacity=cap, t_pixels=t_px,
@@ -161,20 +52,15 @@ def _run(gpu, reg2d, connectivity, cap=0, pixels=None, num_regions=0, stream=Non
     return e, _unsigned(g)
 
 
-def _same(got, want, keys):
-    for k in keys:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
-        assert np.array_equal(got[k], want[k]), k
-
-
 def _check(gpu, name, w, h, connectivity):
     """Everything at capacity E (1 where E is 0: no array may be written then)."""
     want = _reference(name, w, h, connectivity)
     nreg = len(want["degree"]) if "degree" in want else 0
-    e, g = _run(gpu, _base(name, w, h), connectivity, cap=max(want["E"], 1), pixels=_frame(w, h), num_regions=nreg)
+    e, g = _run(gpu, adjacency_base(name, w, h), connectivity, cap=max(want["E"], 1), pixels=frame(w, h),
+                num_regions=nreg)
     assert e == want["E"]
     assert sorted(g) == sorted(k for k in want if k != "E")
-    _same(g, want, [k for k in want if k != "E"])
+    same(g, want, [k for k in want if k != "E"])
     assert (g["edges"][:, 0] < g["edges"][:, 1]).all() and (g["contact"][:, 0] < g["contact"][:, 1]).all()
     return want
 
@@ -242,8 +128,8 @@ def _raw(gpu, reg2d, connectivity, cap, pixels=None, num_regions=0, with_arrays=
     capacity -> (E, {name: all words as uint32}, degree or None)."""
     import torch
     h, w = reg2d.shape
-    t_reg = _to_dev(reg2d.reshape(-1))
-    t_px = _to_dev(pixels) if pixels is not None else None
+    t_reg = to_dev(reg2d.reshape(-1))
+    t_px = to_dev(pixels) if pixels is not None else None
     guard = int(np.full(1, GUARD_WORD, np.uint32).view(np.int32)[0])
     bufs = {}
     if with_arrays:
@@ -254,7 +140,7 @@ def _raw(gpu, reg2d, connectivity, cap, pixels=None, num_regions=0, with_arrays=
     e = gpu.lib().dq_hip_region_adjacency_dev(0, ptr(t_reg), w, h, connectivity, cap, ptr(bufs.get("edges")),
                                               ptr(bufs.get("border")), ptr(bufs.get("contact")), ptr(t_px),
                                               ptr(bufs.get("step")), num_regions, ptr(t_deg), None)
-    return e, {k: _to_host(v, np.uint32) for k, v in bufs.items()}, None if t_deg is None else _to_host(t_deg, np.uint32)
+    return e, {k: to_host(v, np.uint32) for k, v in bufs.items()}, None if t_deg is None else to_host(t_deg, np.uint32)
 
 
 def _heads(bufs, m):
@@ -286,7 +172,7 @@ def test_edge_capacity(gpu, which):
     assert E == 21   # K7: every pair of the seven ids touches
     cap = {"zero": 0, "one": 1, "E-1": E - 1, "E": E, "E+5": E + 5}[which]
     m = min(E, cap)
-    e, bufs, deg = _raw(gpu, _base("noise7", w, h), connectivity, cap, pixels=_frame(w, h), num_regions=nreg)
+    e, bufs, deg = _raw(gpu, adjacency_base("noise7", w, h), connectivity, cap, pixels=frame(w, h), num_regions=nreg)
     assert e == E
     assert np.array_equal(deg[:nreg], want["degree"]) and (deg[nreg:] == GUARD_WORD).all()
     for k, words in bufs.items():
@@ -299,11 +185,11 @@ def test_edge_capacity(gpu, which):
 def test_count_only_call_then_the_full_call(gpu):
     w, h, connectivity = 130, 70, 8
     want = _reference("noise50000", w, h, connectivity)
-    e0, bufs, _ = _raw(gpu, _base("noise50000", w, h), connectivity, cap=0, with_arrays=False)
+    e0, bufs, _ = _raw(gpu, adjacency_base("noise50000", w, h), connectivity, cap=0, with_arrays=False)
     assert e0 == want["E"] and bufs == {}
-    e1, g = _run(gpu, _base("noise50000", w, h), connectivity, cap=e0)
+    e1, g = _run(gpu, adjacency_base("noise50000", w, h), connectivity, cap=e0)
     assert e1 == e0 and sorted(g) == ["border", "contact", "edges"]
-    _same(g, want, ["edges", "border", "contact"])
+    same(g, want, ["edges", "border", "contact"])
 
 
 def test_single_arrays(gpu):
@@ -312,7 +198,7 @@ def test_single_arrays(gpu):
     w, h, connectivity = 65, 3, 8
     want = _reference("noise3", w, h, connectivity)
     E = want["E"]
-    t_reg, t_px = _to_dev(_base("noise3", w, h).reshape(-1)), _to_dev(_frame(w, h))
+    t_reg, t_px = to_dev(adjacency_base("noise3", w, h).reshape(-1)), to_dev(frame(w, h))
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     for k, p in PER.items():
         t = torch.zeros(E * p, dtype=torch.int32, device="cuda:0")
@@ -321,7 +207,7 @@ def test_single_arrays(gpu):
                                                   a["contact"], ptr(t_px) if k == "step" else None, a["step"], 0,
                                                   None, None)
         assert e == E
-        assert np.array_equal(_heads({k: _to_host(t, np.uint32)}, E)[k], want[k]), k
+        assert np.array_equal(_heads({k: to_host(t, np.uint32)}, E)[k], want[k]), k
 
 
 def test_top_bytes_of_the_frame_are_ignored(gpu):
@@ -329,8 +215,8 @@ def test_top_bytes_of_the_frame_are_ignored(gpu):
     want = _reference("noise7", w, h, connectivity)
     top = (fx.xorshift(w * h, seed=fx.SEED + 3) << np.uint32(24)).astype(np.uint32)
     assert len(np.unique(top >> 24)) > 100
-    px = (_frame(w, h) | top).astype(np.uint32)
-    e, g = _run(gpu, _base("noise7", w, h), connectivity, cap=want["E"], pixels=px)
+    px = (frame(w, h) | top).astype(np.uint32)
+    e, g = _run(gpu, adjacency_base("noise7", w, h), connectivity, cap=want["E"], pixels=px)
     assert e == want["E"] and np.array_equal(g["step"], want["step"])
     assert int(want["step"].sum()) > 0 and (want["step"] <= 765 * want["border"].astype(np.uint64)).all()
 
@@ -338,8 +224,8 @@ def test_top_bytes_of_the_frame_are_ignored(gpu):
 def test_same_input_twice_gives_identical_bytes(gpu):
     w, h = 130, 70
     E = _reference("noise50000", w, h, 8)["E"]
-    a = _run(gpu, _base("noise50000", w, h), 8, cap=E, pixels=_frame(w, h), num_regions=50000)
-    b = _run(gpu, _base("noise50000", w, h), 8, cap=E, pixels=_frame(w, h), num_regions=50000)
+    a = _run(gpu, adjacency_base("noise50000", w, h), 8, cap=E, pixels=frame(w, h), num_regions=50000)
+    b = _run(gpu, adjacency_base("noise50000", w, h), 8, cap=E, pixels=frame(w, h), num_regions=50000)
     assert a[0] == b[0] == E
     for k in a[1]:
         assert a[1][k].tobytes() == b[1][k].tobytes(), k
@@ -357,7 +243,7 @@ def test_two_streams_at_once(gpu):
 
     def work(i):
         name, w, h, connectivity = cases[i]
-        results[i] = _run(gpu, _base(name, w, h), connectivity, cap=wants[i]["E"], pixels=_frame(w, h),
+        results[i] = _run(gpu, adjacency_base(name, w, h), connectivity, cap=wants[i]["E"], pixels=frame(w, h),
                           num_regions=len(wants[i]["degree"]), stream=streams[i])
 
     threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
@@ -367,20 +253,20 @@ def test_two_streams_at_once(gpu):
         t.join()
     for want, (e, g) in zip(wants, results):
         assert e == want["E"]
-        _same(g, want, ["edges", "border", "contact", "step", "degree"])
+        same(g, want, ["edges", "border", "contact", "step", "degree"])
 
 
 def test_host_form_equals_the_device_form(gpu):
     w, h = 67, 31
     for name, connectivity in (("noise7", 8), ("permutation", 4)):
         want = _reference(name, w, h, connectivity)
-        reg = _base(name, w, h)
-        g = gpu.region_adjacency(reg, connectivity=connectivity, pixels=_frame(w, h))
-        e, d = _run(gpu, reg, connectivity, cap=want["E"], pixels=_frame(w, h), num_regions=int(reg.max()) + 1)
+        reg = adjacency_base(name, w, h)
+        g = gpu.region_adjacency(reg, connectivity=connectivity, pixels=frame(w, h))
+        e, d = _run(gpu, reg, connectivity, cap=want["E"], pixels=frame(w, h), num_regions=int(reg.max()) + 1)
         assert e == want["E"] and sorted(g) == sorted(d) == ["border", "contact", "degree", "edges", "step"]
-        _same(g, d, sorted(g))
-        _same(g, want, sorted(g))
-    g = gpu.region_adjacency(_base("constant", w, h), num_regions=9)    # no edge at all
+        same(g, d, sorted(g))
+        same(g, want, sorted(g))
+    g = gpu.region_adjacency(adjacency_base("constant", w, h), num_regions=9)    # no edge at all
     assert g["edges"].shape == (0, 2) and g["border"].shape == (0,) and "step" not in g
     assert g["degree"].tolist() == [0] * 9
 
@@ -396,13 +282,13 @@ def test_pipeline_labels_to_regions_to_graph_on_the_device(gpu):
     lab = (((xs // 6) + (ys // 5)) % 3 + 3 * ((xs - w // 2) ** 2 + (ys - h // 2) ** 2 < 90)).astype(np.uint8)
     t_lab = torch.from_numpy(lab.reshape(-1).copy()).to("cuda:0")
     t_reg = torch.empty(w * h, dtype=torch.int32, device="cuda:0")
-    t_px = _to_dev(_frame(w, h))
+    t_px = to_dev(frame(w, h))
     R, _ = gpu.label_regions_device(t_lab, w, h, t_reg, connectivity=8)
     E, _ = gpu.region_adjacency_device(t_reg, w, h, connectivity=8)
     e, g = gpu.region_adjacency_device(t_reg, w, h, connectivity=8, edge_capacity=E, t_pixels=t_px, num_regions=R)
     assert e == E and E > 20
     g = _unsigned(g)
-    reg = _to_host(t_reg, np.uint32).reshape(h, w)
+    reg = to_host(t_reg, np.uint32).reshape(h, w)
     sets = [set() for _ in range(R)]
     for y in range(h):
         for x in range(w):
@@ -418,4 +304,4 @@ def test_pipeline_labels_to_regions_to_graph_on_the_device(gpu):
         got[b].add(a)
     assert got == sets
     assert g["degree"].tolist() == [len(s) for s in sets]
-    _same(g, adjacency_model(reg, 8, _frame(w, h), R), ["edges", "border", "contact", "step", "degree"])
+    same(g, adjacency_model(reg, 8, frame(w, h), R), ["edges", "border", "contact", "step", "degree"])

@@ -21,20 +21,13 @@ import numpy as np
 import pytest
 
 import containment_model as cm
+from region_dev import to_dev
 
 pytestmark = pytest.mark.gpu
 
 NONE = cm.NONE
-ARRAYS = ("depth", "parent", "roots", "child_offsets", "children", "subtree", "enclosed", "order", "pos")
+ARRAYS = cm.ARRAYS
 GUARD = 0x5A5A5A5A
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).to("cuda:0")
 
 
 def _host(t):
@@ -44,9 +37,9 @@ def _host(t):
 
 def run(gpu, reg, area, edges, nregions, outputs=None, stream=None):
     h, w = reg.shape
-    t_edges = _dev(np.asarray(edges, np.uint32).reshape(-1, 2)) if len(edges) else None
+    t_edges = to_dev(np.asarray(edges, np.uint32).reshape(-1, 2)) if len(edges) else None
     nroots, levels, reached, out = gpu.region_containment_device(
-        _dev(reg.astype(np.uint32)), w, h, nregions, _dev(np.asarray(area, np.uint32)), t_edges, outputs=outputs,
+        to_dev(reg.astype(np.uint32)), w, h, nregions, to_dev(np.asarray(area, np.uint32)), t_edges, outputs=outputs,
         stream=stream)
     got = {k: _host(v) for k, v in out.items()}
     got.update(nroots=nroots, levels=levels, reached=reached)
@@ -160,12 +153,12 @@ def _size_patterns(R):
 def test_regions_by_size_alone(gpu, R):
     for name, area in _size_patterns(R):
         want_order, want_rank = cm.size_order(area)
-        order, rank = gpu.regions_by_size_device(_dev(area))
+        order, rank = gpu.regions_by_size_device(to_dev(area))
         assert np.array_equal(_host(order), want_order), (name, R)
         assert np.array_equal(_host(rank), want_rank), (name, R)
-    order, none = gpu.regions_by_size_device(_dev(area), want_rank=False)
+    order, none = gpu.regions_by_size_device(to_dev(area), want_rank=False)
     assert none is None and np.array_equal(_host(order), want_order)
-    none, rank = gpu.regions_by_size_device(_dev(area), want_order=False)
+    none, rank = gpu.regions_by_size_device(to_dev(area), want_order=False)
     assert none is None and np.array_equal(_host(rank), want_rank)
 
 
@@ -186,7 +179,7 @@ def test_random_label_maps_through_the_device_pipeline(gpu, w, h, seed):
     import torch
     nlabels = 2 + (seed * 7 + w) % 5          # 2 .. 6
     conn = 4 if seed % 2 else 8
-    t_lab = _dev(_label_map(w, h, nlabels, seed))
+    t_lab = to_dev(_label_map(w, h, nlabels, seed))
     t_reg = torch.empty(w * h, dtype=torch.int32, device="cuda:0")
     R, stats = gpu.label_regions_device(t_lab, w, h, t_reg, connectivity=conn, stats_capacity=w * h)
     E, _ = gpu.region_adjacency_device(t_reg, w, h, connectivity=conn)
@@ -205,7 +198,7 @@ def test_random_label_maps_through_the_device_pipeline(gpu, w, h, seed):
     mixed = mixed[rng.permutation(len(mixed))]
     swap = rng.random(len(mixed)) < 0.5
     mixed[swap] = mixed[swap][:, ::-1]
-    for e in (_dev(mixed), graph["edges"]):   # (and the call repeated)
+    for e in (to_dev(mixed), graph["edges"]):   # (and the call repeated)
         nroots2, levels2, reached2, out2 = call(e)
         assert (nroots2, levels2, reached2) == (nroots, levels, reached)
         for k in ARRAYS:
@@ -219,7 +212,7 @@ def _raw(gpu, reg, area, edges, R, stream=None):
     h, w = reg.shape
     t = {k: torch.full((R + (k == "child_offsets"),), GUARD, dtype=torch.int64 if k == "enclosed" else torch.int32,
                        device="cuda:0") for k in ARRAYS}
-    t_reg, t_area, t_edges = _dev(reg.astype(np.uint32)), _dev(area), _dev(np.asarray(edges, np.uint32))
+    t_reg, t_area, t_edges = to_dev(reg.astype(np.uint32)), to_dev(area), to_dev(np.asarray(edges, np.uint32))
     levels, reached = ctypes.c_uint32(0), ctypes.c_uint32(0)
     p = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
     torch.cuda.synchronize()

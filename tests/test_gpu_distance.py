@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import distance_model as dm
+from region_dev import to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -33,14 +34,6 @@ def coord(x, y):
     return x | y << 16
 
 
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).to("cuda:0")
-
-
 def _host(name, t):
     a = t.cpu().numpy()
     return a.view({"dist": np.uint16, "core": np.uint8}.get(name, np.uint32))
@@ -48,13 +41,14 @@ def _host(name, t):
 
 def distance(gpu, reg, nreg, rule=0, outputs=None, stream=None):
     h, w = reg.shape
-    out = gpu.region_distance_device(_dev(reg.astype(np.uint32)), w, h, nreg, rule=rule, outputs=outputs, stream=stream)
+    out = gpu.region_distance_device(to_dev(reg.astype(np.uint32)), w, h, nreg, rule=rule, outputs=outputs,
+                                     stream=stream)
     return {k: _host(k, v) for k, v in out.items()}
 
 
 def cores(gpu, reg, nreg, rule=0, connectivity=8, outputs=None):
     h, w = reg.shape
-    kept, out = gpu.region_cores_device(_dev(reg.astype(np.uint32)), w, h, nreg, rule=rule, connectivity=connectivity,
+    kept, out = gpu.region_cores_device(to_dev(reg.astype(np.uint32)), w, h, nreg, rule=rule, connectivity=connectivity,
                                         outputs=outputs)
     got = {k: _host(k, v) for k, v in out.items()}
     got["kept"] = kept
@@ -250,7 +244,7 @@ def test_cores_of_blobs(gpu, gap):
 
 
 # Every output NULL in turn; 64 guard bytes behind every output given.
-def _guarded(nbytes):
+def _guarded(nbytes):   # (bytes, not region_dev's words: the outputs here are u8, u16 and u32)
     import torch
     t = torch.full((nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda:0")
     return t
@@ -259,7 +253,7 @@ def _guarded(nbytes):
 def _raw(gpu, call, reg, nreg, names, skip, extra, stream=None):
     h, w = reg.shape
     size = {"dist": 2 * h * w, "core": h * w, "cored": 4 * h * w, "bbox": 16 * nreg}
-    t_reg = _dev(reg)
+    t_reg = to_dev(reg)
     t = {k: _guarded(size.get(k, 4 * nreg)) for k in names if k not in skip}
     p = lambda k: ctypes.c_void_p(t[k].data_ptr()) if k in t else None  # noqa: E731
     import torch
@@ -299,7 +293,7 @@ def test_cored_in_place(gpu):
     reg = _two_blobs(50)
     v = dm.region_values(reg, 2)
     want = dm.region_cores(reg, 2, v["centre"], 4)
-    t_reg = _dev(reg)
+    t_reg = to_dev(reg)
     kept, out = gpu.region_cores_device(t_reg, reg.shape[1], reg.shape[0], 2, connectivity=4, outputs=("cored",),
                                         t_cored=t_reg)
     assert kept == want["kept"] and np.array_equal(_host("cored", t_reg), want["cored"])
@@ -334,7 +328,7 @@ def test_two_calls_overlap_on_two_streams(gpu):
                     got[i] = distance(gpu, reg, nreg, stream=streams[i])
                 else:
                     h, w = reg.shape
-                    kept, out = gpu.region_cores_device(_dev(reg), w, h, nreg, stream=streams[i])
+                    kept, out = gpu.region_cores_device(to_dev(reg), w, h, nreg, stream=streams[i])
                     got[i] = dict({k: _host(k, v) for k, v in out.items()}, kept=kept)
         except BaseException as e:   # noqa: B036 (reported by the test's thread)
             errors.append(e)

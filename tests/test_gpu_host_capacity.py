@@ -19,8 +19,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_gpu_merge import NONE, _frame, _noise
-from test_gpu_windows import wmap
+from merge_model import NONE
+from region_inputs import frame, noise, wmap
 
 pytestmark = pytest.mark.gpu
 
@@ -57,8 +57,8 @@ def _prefix_only(got, want, per, cap):
 
 
 def _labels():
-    lab = np.ascontiguousarray(_noise(W, H, 3), np.uint32)
-    return lab, np.ascontiguousarray(_frame(W, H), np.uint32)
+    lab = np.ascontiguousarray(noise(W, H, 3, seed=1), np.uint32)
+    return lab, np.ascontiguousarray(frame(W, H), np.uint32)
 
 
 # ---------------------------------------------------------------------------
@@ -154,7 +154,7 @@ LISTS = ("coords", "index", "colors")
 
 
 def _windows(gpu, reg, w, h, R, cap, room=None, expand=EXPAND):
-    px = np.ascontiguousarray(_frame(w, h), np.uint32)
+    px = np.ascontiguousarray(frame(w, h), np.uint32)
     o = {k: _out(cap if room is None else room) for k in LISTS}
     o["offsets"] = _out(R + 1)
     rc = gpu.lib().dq_hip_region_windows(_p(reg), w, h, R, BLOCK, expand, None, None, 0, _p(o["offsets"]), cap,
@@ -218,7 +218,7 @@ def test_refused_pixels(gpu):
     reg[0] = reg[63] = np.arange(4)
     o = {k: _out(w * h) for k in LISTS}
     o["offsets"] = _out(R + 1)
-    px = np.ascontiguousarray(_frame(w, h), np.uint32)
+    px = np.ascontiguousarray(frame(w, h), np.uint32)
     rc = gpu.lib().dq_hip_region_pixels(_p(reg), w, h, R, _p(o["offsets"]), _p(o["coords"]), _p(o["index"]), _p(px),
                                         _p(o["colors"]))
     assert rc == -2

@@ -1,18 +1,13 @@
 """GPU: merging regions over their adjacency graph (include/dq_hip.h, "region
 merge") and the host pipeline labels -> segments.
 
-The reference is the numpy model below, written against the definition and
-using none of the code under test: regions by union-find over equal-label
-neighbours numbered by first pixel, edges by np.unique over the neighbour pairs
-with different ids, and the merge itself round by round -- 8.8 fixed-point
-means by integer division, keys (d << 32 | other) reduced by np.minimum.at,
-the link rule, roots by pointer jumping, stats folded by np.add.at /
-np.minimum.at / np.maximum.at, final ids by the rank of the roots' first
-pixels.  Equality is exact everywhere: array_equal on the map, remap and every
-stats array, == on R' and the rounds.  On the 64 x 48 noise map the model's
-own R' and rounds are pinned to the figures it gave when the definition was
-fixed (from R = 809: 486 in 1 round, 104 in 2, 1 in 4, 570 in 4, 315 in 5,
-809 in 0), so a weakened model cannot pass.
+The reference is merge_model of merge_model.py on the regions of regions_model
+(regions_model.py) and the edges of edges_model (adjacency_model.py), written
+against the definition and using none of the code under test; the named inputs
+are merge_inputs of region_inputs.py.  Equality is exact everywhere:
+array_equal on the map, remap and every stats array, == on R' and the rounds.
+test_merge_model.py pins the model's own R' and rounds on the 64 x 48 noise
+map, so a weakened model cannot pass.
 
 There is no fixture of batman labels under tests/golden (only the PNG), so the
 host pipeline is checked on the noise maps alone.
@@ -33,214 +28,24 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
+from adjacency_model import edges_model
+from merge_model import NONE, merge_model
+from region_dev import same, to_dev, to_host
+from region_inputs import merge_inputs, merge_labels_and_frame
+from regions_model import regions_model
 
 pytestmark = pytest.mark.gpu
 
 GUARD_WORD = 0xA5A5A5A5
-NONE = 0xFFFFFFFF              # max_dist: no limit
 ALL = 1 << 31                  # min_area above every area: everything is restless
 PER = {"area": 1, "bbox": 4, "first": 1, "sums": 6}   # 4-byte words per region
-NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
-
-
-# ---------------------------------------------------------------------------
-# The reference.
-def _neighbour_pairs(w, h, connectivity):
-    idx = np.arange(h * w, dtype=np.int64).reshape(h, w)
-    pairs = [(idx[:, :-1], idx[:, 1:]), (idx[:-1, :], idx[1:, :])]
-    if connectivity == 8:
-        pairs += [(idx[:-1, 1:], idx[1:, :-1]), (idx[:-1, :-1], idx[1:, 1:])]
-    else:
-        assert connectivity == 4
-    return (np.concatenate([a.reshape(-1) for a, _ in pairs]), np.concatenate([b.reshape(-1) for _, b in pairs]))
-
-
-def regions_model(lab2d, connectivity, pixels):
-    """(flat region ids numbered by first pixel, stats) of a 2-D label map."""
-    lab2d = np.asarray(lab2d)
-    h, w = lab2d.shape
-    n = h * w
-    lab = lab2d.reshape(-1)
-    p, q = _neighbour_pairs(w, h, connectivity)
-    same = lab[p] == lab[q]
-    up = list(range(n))
-
-    def find(i):
-        while up[i] != i:
-            up[i] = up[up[i]]
-            i = up[i]
-        return i
-    for a, b in zip(p[same].tolist(), q[same].tolist()):
-        ra, rb = find(a), find(b)
-        if ra != rb:
-            up[max(ra, rb)] = min(ra, rb)      # the root is the lowest pixel: the region's first
-    root = np.array([find(i) for i in range(n)], np.int64)
-    firsts, reg = np.unique(root, return_inverse=True)
-    return reg.reshape(-1).astype(np.uint32), stats_model(reg.reshape(-1), w, pixels, firsts)
-
-
-def stats_model(reg, w, pixels, firsts=None):
-    """area, first, bbox, sums of a flat id map whose ids are 0 .. R-1."""
-    reg = np.asarray(reg).astype(np.int64)
-    n, R = len(reg), int(reg.max()) + 1
-    ys, xs = np.divmod(np.arange(n, dtype=np.int64), w)
-    first = np.full(R, n, np.int64)
-    np.minimum.at(first, reg, np.arange(n, dtype=np.int64))
-    assert firsts is None or np.array_equal(first, firsts)
-    bbox = np.zeros((R, 4), np.int64)
-    bbox[:, 0], bbox[:, 1] = w, n
-    np.minimum.at(bbox[:, 0], reg, xs)
-    np.minimum.at(bbox[:, 1], reg, ys)
-    np.maximum.at(bbox[:, 2], reg, xs)
-    np.maximum.at(bbox[:, 3], reg, ys)
-    px = np.asarray(pixels, np.uint32).reshape(-1)
-    sums = np.zeros((R, 3), np.uint64)
-    for c, shift in enumerate((16, 8, 0)):
-        np.add.at(sums[:, c], reg, ((px >> shift) & 0xFF).astype(np.uint64))
-    return {"area": np.bincount(reg, minlength=R).astype(np.uint32), "first": first.astype(np.uint32),
-            "bbox": bbox.astype(np.uint32), "sums": sums}
-
-
-def edges_model(reg, w, h, connectivity):
-    """The (E, 2) pairs a < b of ids that touch, sorted."""
-    reg = np.asarray(reg).astype(np.int64)
-    p, q = _neighbour_pairs(w, h, connectivity)
-    a, b = np.minimum(reg[p], reg[q]), np.maximum(reg[p], reg[q])
-    keep = a != b
-    return np.unique(np.stack([a[keep], b[keep]], axis=1), axis=0).astype(np.uint32).reshape(-1, 2)
-
-
-def merge_model(reg, area, first, sums, bbox, edges, min_area, max_dist=NONE, max_rounds=0):
-    """dict(R, rounds, regions, remap, area, first, sums, bbox) by the definition."""
-    reg = np.asarray(reg).astype(np.int64)
-    R = len(area)
-    area = np.asarray(area).astype(np.int64).copy()
-    first = np.asarray(first).astype(np.int64).copy()
-    sums = np.asarray(sums).astype(np.int64).copy()
-    bbox = np.asarray(bbox).astype(np.int64).copy()
-    ea = np.asarray(edges).reshape(-1, 2)[:, 0].astype(np.int64)
-    eb = np.asarray(edges).reshape(-1, 2)[:, 1].astype(np.int64)
-    comp = np.arange(R, dtype=np.int64)
-    ids = np.arange(R, dtype=np.int64)
-    live = np.ones(R, bool)
-    rounds = 0
-    while not (max_rounds and rounds >= max_rounds):
-        restless = live & (area < min_area)                                   # 1
-        mean = (256 * sums) // np.maximum(area, 1)[:, None]                   # 2
-        A, B = comp[ea], comp[eb]
-        d = np.abs(mean[A] - mean[B]).sum(axis=1)                             # 3
-        ok = (A != B) & (d <= max_dist)                                       # 4
-        A, B, d = A[ok], B[ok], d[ok].astype(np.uint64)
-        best = np.full(R, NO_KEY, np.uint64)
-        for X, Y in ((A, B), (B, A)):
-            offered = restless[X]
-            np.minimum.at(best, X[offered], (d[offered] << np.uint64(32)) | Y[offered].astype(np.uint64))
-        has = best != NO_KEY                                                   # 5
-        target = (best & np.uint64(0xFFFFFFFF)).astype(np.int64)
-        target[~has] = ids[~has]
-        stays = has & has[target] & (target[target] == ids) & (ids < target)
-        links = has & ~stays
-        if not links.any():                                                    # 6
-            break
-        parent = np.where(links, target, ids)                                  # 7
-        root, jumps = parent, 0
-        while not np.array_equal(root[root], root):
-            root, jumps = root[root], jumps + 1
-            assert jumps <= 32, "a cycle in parent"
-        moved = np.nonzero(live & (root != ids))[0]
-        np.add.at(area, root[moved], area[moved])
-        np.add.at(sums, root[moved], sums[moved])
-        np.minimum.at(first, root[moved], first[moved])
-        np.minimum.at(bbox[:, 0], root[moved], bbox[moved, 0])
-        np.minimum.at(bbox[:, 1], root[moved], bbox[moved, 1])
-        np.maximum.at(bbox[:, 2], root[moved], bbox[moved, 2])
-        np.maximum.at(bbox[:, 3], root[moved], bbox[moved, 3])
-        live[moved] = False
-        comp = root[comp]
-        rounds += 1
-    roots = np.nonzero(live)[0]
-    assert np.array_equal(np.unique(comp), roots)
-    order = roots[np.argsort(first[roots], kind="stable")]
-    newid = np.full(R, -1, np.int64)
-    newid[order] = np.arange(len(order))
-    remap = newid[comp]
-    out = {"R": len(order), "rounds": rounds, "regions": remap[reg].astype(np.uint32), "remap": remap.astype(np.uint32),
-           "area": area[order].astype(np.uint32), "first": first[order].astype(np.uint32),
-           "sums": sums[order].astype(np.uint64), "bbox": bbox[order].astype(np.uint32)}
-    for v in out.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return out
-
-
-# ---------------------------------------------------------------------------
-# Inputs: a label map, its frame, the model's regions and edges.
-@functools.lru_cache(maxsize=None)
-def _frame(w, h):
-    px = fx.xorshift(w * h, seed=fx.SEED + 77)   # 0x00RRGGBB
-    px.setflags(write=False)
-    return px
-
-
-def _noise(w, h, k):
-    return (fx.xorshift(w * h, seed=fx.SEED + 1) % np.uint32(k)).astype(np.uint32).reshape(h, w)
-
-
-def _labels_and_frame(name):
-    """(labels2d, frame, connectivity) of a named case."""
-    if name == "noise64x48":
-        return _noise(64, 48, 4), _frame(64, 48), 8
-    if name == "noise96x80":
-        return _noise(96, 80, 4), _frame(96, 80), 4
-    if name == "noise97x41":
-        return _noise(97, 41, 3), _frame(97, 41), 8
-    if name == "chain":         # every pixel its own region, one colour: every distance 0
-        return np.arange(2048, dtype=np.uint32).reshape(1, 2048), np.full(2048, 0x00406080, np.uint32), 8
-    if name == "islands":       # background 0, a one-pixel island at every even (x, y) of 64 x 64
-        ys, xs = np.mgrid[0:64, 0:64]
-        island = (xs % 2 == 0) & (ys % 2 == 0)
-        lab = np.where(island, 1 + (ys // 2) * 32 + xs // 2, 0).astype(np.uint32)
-        px = np.where(island.reshape(-1), _frame(64, 64), np.uint32(0x00102030)).astype(np.uint32)
-        return lab, px, 8
-    if name == "stripes":       # 16 vertical stripes 4 wide; 2i and 2i + 1 are 1 level apart, pairs 30 apart
-        ys, xs = np.mgrid[0:12, 0:64]
-        lab = (xs // 4).astype(np.uint32)
-        level = 30 * (lab // 2) + (lab % 2)      # <= 211
-        return lab, (level * np.uint32(0x010101)).astype(np.uint32).reshape(-1), 4
-    if name == "one":
-        return np.zeros((5, 7), np.uint32), _frame(7, 5), 8
-    raise KeyError(name)
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(name):
-    lab, px, connectivity = _labels_and_frame(name)
-    h, w = lab.shape
-    reg, st = regions_model(lab, connectivity, px)
-    inp = dict(st, w=w, h=h, connectivity=connectivity, labels=lab, pixels=px, regions=reg,
-               edges=edges_model(reg, w, h, connectivity), R=len(st["area"]))
-    for v in inp.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return inp
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(name, min_area, max_dist=NONE, max_rounds=0):
-    i = _inputs(name)
+    i = merge_inputs(name)
     return merge_model(i["regions"], i["area"], i["first"], i["sums"], i["bbox"], i["edges"], min_area, max_dist,
                        max_rounds)
-
-
-def _to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    signed = {"u4": np.int32, "u8": np.int64}[a.dtype.str[1:]]
-    return torch.from_numpy(a.view(signed).copy()).to("cuda:0")
-
-
-def _to_host(t, dtype=np.uint32):
-    return t.cpu().numpy().view(dtype)
 
 
 def _run(gpu, inp, min_area, max_dist=NONE, max_rounds=0, edges=None, regions=None, stream=None):
@@ -248,16 +53,16 @@ def _run(gpu, inp, min_area, max_dist=NONE, max_rounds=0, edges=None, regions=No
     -> (R', rounds, outputs as unsigned numpy)."""
     import torch
     edges = inp["edges"] if edges is None else edges
-    t = {k: _to_dev(inp[k].reshape(-1)) for k in ("area", "first", "sums", "bbox")}
-    t_reg = _to_dev(inp["regions"] if regions is None else regions)
-    t_edges = _to_dev(edges.reshape(-1)) if len(edges) else None
+    t = {k: to_dev(inp[k].reshape(-1)) for k in ("area", "first", "sums", "bbox")}
+    t_reg = to_dev(inp["regions"] if regions is None else regions)
+    t_edges = to_dev(edges.reshape(-1)) if len(edges) else None
     if stream is not None:   # (the tensors above were filled on the current stream)
         stream.wait_stream(torch.cuda.current_stream())
     r, rounds, out = gpu.merge_regions_device(t_reg, inp["R"], t["area"], t["first"], t["sums"], t_edges, min_area,
                                               max_dist=max_dist, max_rounds=max_rounds, t_bbox=t["bbox"],
                                               num_edges=len(edges), stats_capacity=inp["R"], stream=stream)
     assert out["regions"] is t_reg
-    return r, rounds, {k: _to_host(v, np.uint64 if k == "sums" else np.uint32) for k, v in out.items()}
+    return r, rounds, {k: to_host(v, np.uint64 if k == "sums" else np.uint32) for k, v in out.items()}
 
 
 KEYS = ("regions", "remap", "area", "first", "sums", "bbox")
@@ -266,30 +71,17 @@ KEYS = ("regions", "remap", "area", "first", "sums", "bbox")
 def _same(r, rounds, got, want):
     assert (r, rounds) == (want["R"], want["rounds"])
     assert sorted(got) == sorted(KEYS)
-    for k in KEYS:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
-        assert np.array_equal(got[k], want[k]), k
+    same(got, want, KEYS)
 
 
 # ---------------------------------------------------------------------------
 # 1. Noise over a parameter grid.
 GRID = [(2, NONE), (10, NONE), (ALL, NONE), (10, 20000), (ALL, 30000), (ALL, 0)]
-PINNED = {(2, NONE): (486, 1), (10, NONE): (104, 2), (ALL, NONE): (1, 4), (10, 20000): (570, 4),
-          (ALL, 30000): (315, 5), (ALL, 0): (809, 0)}
-
-
-def test_the_model_reproduces_the_pinned_figures():
-    assert _inputs("noise64x48")["R"] == 809
-    for params, figures in PINNED.items():
-        want = _reference("noise64x48", *params)
-        assert (want["R"], want["rounds"]) == figures, params
-
-
 @pytest.mark.parametrize("params", GRID, ids=lambda p: "area%d-dist%d" % p)
 @pytest.mark.parametrize("name", ["noise64x48", "noise96x80", "noise97x41"])
 def test_noise_grid(gpu, name, params):
     want = _reference(name, *params)
-    r, rounds, got = _run(gpu, _inputs(name), *params)
+    r, rounds, got = _run(gpu, merge_inputs(name), *params)
     _same(r, rounds, got, want)
     assert int(got["area"].sum()) == len(got["regions"])
 
@@ -297,7 +89,7 @@ def test_noise_grid(gpu, name, params):
 # 2. Chain and ties.
 @pytest.mark.parametrize("max_rounds", [0, 1])
 def test_chain_of_2047_links_in_one_round(gpu, max_rounds):
-    inp = _inputs("chain")
+    inp = merge_inputs("chain")
     assert inp["R"] == 2048 and len(inp["edges"]) == 2047
     want = _reference("chain", ALL, NONE, max_rounds)
     assert (want["R"], want["rounds"]) == (1, 1)
@@ -308,7 +100,7 @@ def test_chain_of_2047_links_in_one_round(gpu, max_rounds):
 
 # 3. One hot root.
 def test_a_thousand_islands_fold_into_one_root(gpu):
-    inp = _inputs("islands")
+    inp = merge_inputs("islands")
     assert inp["R"] == 1025 and int((inp["area"] == 1).sum()) == 1024
     want = _reference("islands", 2)
     assert (want["R"], want["rounds"]) == (1, 1)
@@ -321,7 +113,7 @@ def test_a_thousand_islands_fold_into_one_root(gpu):
 
 # 4. Mutual pairs.
 def test_mutual_pairs_keep_the_lower_id(gpu):
-    inp = _inputs("stripes")
+    inp = merge_inputs("stripes")
     assert inp["R"] == 16 and (inp["area"] == 48).all()
     want = _reference("stripes", 49)     # above a stripe's area, below a pair's
     assert (want["R"], want["rounds"]) == (8, 1)
@@ -337,7 +129,7 @@ def test_round_limit(gpu, max_rounds):
     assert _reference("noise64x48", ALL, 30000)["rounds"] >= 4
     want = _reference("noise64x48", ALL, 30000, max_rounds)
     assert want["rounds"] == max_rounds
-    r, rounds, got = _run(gpu, _inputs("noise64x48"), ALL, 30000, max_rounds)
+    r, rounds, got = _run(gpu, merge_inputs("noise64x48"), ALL, 30000, max_rounds)
     _same(r, rounds, got, want)
 
 
@@ -383,7 +175,7 @@ def test_star_takes_a_round_per_leaf(gpu):
 # 6. Edge list robustness.
 @pytest.mark.parametrize("how", ["swapped", "shuffled", "three_times"])
 def test_edge_list_order_and_duplicates_do_not_matter(gpu, how):
-    inp = _inputs("noise96x80")
+    inp = merge_inputs("noise96x80")
     e = inp["edges"]
     if how == "swapped":
         e = e[:, ::-1].copy()
@@ -403,10 +195,10 @@ def _raw(gpu, inp, min_area, cap, which=KEYS[2:], remap=True, in_place=True, off
     capacity -> (R', rounds, map, {name: all words as uint32}, remap words)."""
     import torch
     guard = int(np.full(1, GUARD_WORD, np.uint32).view(np.int32)[0])
-    t = {k: _to_dev(inp[k].reshape(-1)) for k in ("area", "first", "sums", "bbox", "edges")}
+    t = {k: to_dev(inp[k].reshape(-1)) for k in ("area", "first", "sums", "bbox", "edges")}
     n = len(inp["regions"])
     t_reg = torch.full((n + 8,), guard, dtype=torch.int32, device="cuda:0")
-    t_reg[offset:offset + n] = _to_dev(inp["regions"])       # offset 1: the map is not 16-byte aligned
+    t_reg[offset:offset + n] = to_dev(inp["regions"])       # offset 1: the map is not 16-byte aligned
     t_out = t_reg if in_place else torch.full((n + 8,), guard, dtype=torch.int32, device="cuda:0")
     bufs = {k: torch.full(((cap + 8) * PER[k],), guard, dtype=torch.int32, device="cuda:0") for k in which}
     t_remap = torch.full((inp["R"] + 8,), guard, dtype=torch.int32, device="cuda:0") if remap else None
@@ -418,11 +210,11 @@ def _raw(gpu, inp, min_area, cap, which=KEYS[2:], remap=True, in_place=True, off
                                            ptr(bufs.get("area")), ptr(bufs.get("bbox")), ptr(bufs.get("first")),
                                            ptr(bufs.get("sums")), ctypes.byref(rounds), None)
     if not in_place:
-        assert np.array_equal(_to_host(t_reg)[offset:offset + n], inp["regions"])   # the input map is left alone
-    words = _to_host(t_out)
+        assert np.array_equal(to_host(t_reg)[offset:offset + n], inp["regions"])   # the input map is left alone
+    words = to_host(t_out)
     assert (words[:offset] == GUARD_WORD).all() and (words[offset + n:] == GUARD_WORD).all()
-    return (r, rounds.value, words[offset:offset + n], {k: _to_host(v) for k, v in bufs.items()},
-            None if t_remap is None else _to_host(t_remap))
+    return (r, rounds.value, words[offset:offset + n], {k: to_host(v) for k, v in bufs.items()},
+            None if t_remap is None else to_host(t_remap))
 
 
 def _heads(bufs, m):
@@ -435,7 +227,7 @@ def _heads(bufs, m):
 
 @pytest.mark.parametrize("which", ["zero", "one", "R-1", "R", "R+3"])
 def test_stats_capacity(gpu, which):
-    inp, want = _inputs("noise64x48"), _reference("noise64x48", 10)
+    inp, want = merge_inputs("noise64x48"), _reference("noise64x48", 10)
     R2 = want["R"]
     cap = {"zero": 0, "one": 1, "R-1": R2 - 1, "R": R2, "R+3": R2 + 3}[which]
     m = min(R2, cap)
@@ -451,7 +243,7 @@ def test_stats_capacity(gpu, which):
 
 @pytest.mark.parametrize("which", ["area", "bbox", "first", "sums"])
 def test_each_stats_pointer_alone(gpu, which):
-    inp, want = _inputs("noise97x41"), _reference("noise97x41", 10)
+    inp, want = merge_inputs("noise97x41"), _reference("noise97x41", 10)
     r, rounds, reg, bufs, _ = _raw(gpu, inp, 10, want["R"], which=(which,))
     assert (r, rounds) == (want["R"], want["rounds"]) and np.array_equal(reg, want["regions"])
     assert np.array_equal(_heads(bufs, want["R"])[which], want[which])
@@ -461,7 +253,7 @@ def test_each_stats_pointer_alone(gpu, which):
 @pytest.mark.parametrize("in_place", [True, False])
 @pytest.mark.parametrize("offset", [0, 1])
 def test_output_map_in_place_or_apart_aligned_or_not_without_remap(gpu, in_place, offset):
-    inp, want = _inputs("noise97x41"), _reference("noise97x41", 10)     # 3977 pixels: a tail of one
+    inp, want = merge_inputs("noise97x41"), _reference("noise97x41", 10)     # 3977 pixels: a tail of one
     r, rounds, reg, bufs, remap = _raw(gpu, inp, 10, want["R"], remap=False, in_place=in_place, offset=offset)
     assert remap is None and (r, rounds) == (want["R"], want["rounds"])
     assert np.array_equal(reg, want["regions"])
@@ -471,7 +263,7 @@ def test_output_map_in_place_or_apart_aligned_or_not_without_remap(gpu, in_place
 
 # 8. Degenerate inputs.
 def test_one_region_no_edge(gpu):
-    inp = _inputs("one")
+    inp = merge_inputs("one")
     assert inp["R"] == 1 and len(inp["edges"]) == 0
     r, rounds, got = _run(gpu, inp, ALL)
     _same(r, rounds, got, _reference("one", ALL))
@@ -479,7 +271,7 @@ def test_one_region_no_edge(gpu):
 
 
 def test_min_area_zero_is_the_identity_on_a_raster_numbered_map(gpu):
-    inp = _inputs("noise64x48")
+    inp = merge_inputs("noise64x48")
     r, rounds, got = _run(gpu, inp, 0)
     assert (r, rounds) == (inp["R"], 0)
     assert np.array_equal(got["regions"], inp["regions"]) and np.array_equal(got["remap"], np.arange(inp["R"]))
@@ -488,7 +280,7 @@ def test_min_area_zero_is_the_identity_on_a_raster_numbered_map(gpu):
 
 
 def test_permuted_ids_come_out_numbered_by_first(gpu):
-    base = _inputs("noise64x48")
+    base = merge_inputs("noise64x48")
     perm = np.argsort(fx.xorshift(base["R"], seed=fx.SEED + 5), kind="stable").astype(np.uint32)   # old -> new id
     inv = np.argsort(perm)
     inp = dict(base, regions=perm[base["regions"]], edges=perm[base["edges"]],
@@ -510,7 +302,7 @@ def test_two_streams_at_once(gpu):
     streams = [torch.cuda.Stream(device="cuda:0") for _ in cases]
     results = [None, None]
     wants = [_reference(*c) for c in cases]   # (the models, before the threads start)
-    inps = [_inputs(c[0]) for c in cases]
+    inps = [merge_inputs(c[0]) for c in cases]
     torch.cuda.synchronize()
 
     def work(i):
@@ -530,7 +322,7 @@ def test_two_streams_at_once(gpu):
 @pytest.mark.parametrize("connectivity", [4, 8])
 @pytest.mark.parametrize("name", ["noise64x48", "noise97x41"])
 def test_segment_labels_equals_the_model_pipeline(gpu, name, connectivity, dtype):
-    lab, px, _ = _labels_and_frame(name)
+    lab, px, _ = merge_labels_and_frame(name)
     h, w = lab.shape
     reg, st = regions_model(lab, connectivity, px)
     want = merge_model(reg, st["area"], st["first"], st["sums"], st["bbox"], edges_model(reg, w, h, connectivity),

@@ -1,9 +1,9 @@
 """GPU: the pixel lists of a region map (include/dq_hip.h, "pixel lists"), their
 inverse and the region map -> per-region quant -> painted frame pipeline.
 
-The reference is the numpy model below, written against the definition and
-using none of the code under test: a stable argsort of the ids, bincount and
-cumsum for the offsets, the lists by fancy indexing.  The pipeline is checked
+The reference is lists_model of pixels_model.py, written against the definition
+and using none of the code under test; the maps are pixels_map of
+region_inputs.py.  The pipeline is checked
 against the CPU oracle's weighted quant_recurse on each region's pixels in
 raster order, and against quant_weighted_regions_device on the same lists.
 Equality is exact everywhere: array_equal on every array, == on every scalar.
@@ -25,126 +25,16 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
-from test_gpu_merge import _frame, _noise, regions_model
+from pixels_model import lists_model, rows_total
+from region_dev import body, guarded, same, to_dev, to_host
+from region_inputs import frame, pixels_map, with_gaps
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 8
 FILL = 0xA5A5A5A5
 ARRAYS = ("index", "coords", "colors")
-
-
-# ---------------------------------------------------------------------------
-# The reference.
-def lists_model(reg2d, R, pixels):
-    reg2d = np.asarray(reg2d)
-    h, w = reg2d.shape
-    regions = reg2d.reshape(-1).astype(np.int64)
-    order = np.argsort(regions, kind="stable")
-    offsets = np.concatenate([[0], np.cumsum(np.bincount(regions, minlength=R))])
-    out = {"offsets": offsets.astype(np.uint32), "index": order.astype(np.uint32),
-           "coords": ((order % w) | (order // w) << 16).astype(np.uint32),
-           "colors": np.asarray(pixels, np.uint32).reshape(-1)[order]}
-    for v in out.values():
-        v.setflags(write=False)
-    return out
-
-
-def rows_total(reg2d):
-    """T of the definition: over the ids present, last row - first row + 1."""
-    reg2d = np.asarray(reg2d)
-    ys = np.repeat(np.arange(reg2d.shape[0]), reg2d.shape[1])
-    ids = reg2d.reshape(-1).astype(np.int64)
-    lo, hi = np.full(ids.max() + 1, 1 << 40), np.full(ids.max() + 1, -1)
-    np.minimum.at(lo, ids, ys)
-    np.maximum.at(hi, ids, ys)
-    return int((hi - lo + 1)[hi >= 0].sum())
-
-
-# ---------------------------------------------------------------------------
-# Inputs.
-def _permuted(reg2d, seed):
-    R = int(reg2d.max()) + 1
-    perm = np.argsort(fx.xorshift(R, seed=fx.SEED + seed), kind="stable").astype(np.uint32)
-    return perm[reg2d]
-
-
-@functools.lru_cache(maxsize=None)
-def _map(name):
-    """(region ids (H, W) uint32, R) of a named case."""
-    if name.endswith("-permuted"):
-        reg, R = _map(name[:-len("-permuted")])
-        return _permuted(reg, 5), R
-    if name.startswith("noise"):
-        w, h, k, conn = {"noise64x48": (64, 48, 4, 8), "noise96x80": (96, 80, 4, 4), "noise97x41": (97, 41, 3, 8),
-                         "noise512x300": (512, 300, 16, 4)}[name]
-        lab = (fx.xorshift(w * h, seed=fx.SEED + 1) % np.uint32(k)).astype(np.uint32).reshape(h, w)
-        assert name == "noise512x300" or np.array_equal(lab, _noise(w, h, k))
-        reg, _ = regions_model(lab, conn, _frame(w, h))
-        reg = reg.reshape(h, w)
-    elif name.startswith("rows"):         # three rows (or as given) of a width around the wave
-        w, h = {"rows1x7": (1, 7), "rows3x5": (3, 5), "rows63": (63, 3), "rows64": (64, 3), "rows65": (65, 3),
-                "rows129": (129, 3)}[name]
-        lab = (fx.xorshift(w * h, seed=fx.SEED + 9) % np.uint32(3)).astype(np.uint32).reshape(h, w)
-        reg = regions_model(lab, 4, _frame(w, h))[0].reshape(h, w)
-    elif name == "stripes":               # not connected: id x % 3 in every row, T = 15 <= n
-        reg = np.tile(np.arange(200, dtype=np.uint32) % 3, (5, 1))
-        assert rows_total(reg) == 15
-    elif name == "comb":                  # two combs whose teeth interlock: A B A B in every middle row
-        ys, xs = np.mgrid[0:21, 0:150]
-        reg = np.where((ys == 0) | ((xs % 2 == 0) & (ys < 20)), 0, 1).astype(np.uint32)
-    elif name == "rings":                 # ring i leaves a row on the left and re-enters it on the right
-        ys, xs = np.mgrid[0:30, 0:70]
-        reg = np.minimum(np.minimum(xs, 69 - xs), np.minimum(ys, 29 - ys)).astype(np.uint32)
-    elif name == "one":
-        reg = np.zeros((5, 7), np.uint32)
-    elif name == "each":                  # R = n
-        reg = np.arange(64 * 48, dtype=np.uint32).reshape(48, 64)
-    elif name == "line":                  # 2048 wide, 1 tall: one wave walks 32 chunks
-        reg = (np.arange(2048, dtype=np.uint32) // 5).reshape(1, 2048)
-    elif name == "column":                # 1 wide, 2048 tall: a wave per pixel
-        reg = (np.arange(2048, dtype=np.uint32) // 7).reshape(2048, 1)
-    elif name == "big":                   # a background of more than 131071 pixels and 300 islands of 3 x 3
-        reg = np.zeros((300, 512), np.uint32)
-        for i in range(300):
-            x, y = 4 + 20 * (i % 25), 4 + 24 * (i // 25)
-            reg[y:y + 3, x:x + 3] = 1 + i
-        reg = _relabel_by_first(reg)
-        assert int((reg == 0).sum()) > 131071 and int(reg.max()) == 300
-    else:
-        raise KeyError(name)
-    reg = np.ascontiguousarray(reg, np.uint32)
-    reg.setflags(write=False)
-    assert rows_total(reg) <= reg.size, name
-    return reg, int(reg.max()) + 1
-
-
-def _relabel_by_first(reg):
-    _, first, inv = np.unique(reg.reshape(-1), return_index=True, return_inverse=True)
-    return np.argsort(np.argsort(first))[inv].reshape(reg.shape).astype(np.uint32)
-
-
-def _with_gaps(reg, front, middle, end):
-    """The same map with `front` unused ids before the first id, `middle`
-    after every id below the median and `end` behind the last one."""
-    R = int(reg.max()) + 1
-    ids = np.arange(R, dtype=np.int64)
-    new = front + ids + middle * np.minimum(ids, R // 2)
-    return new.astype(np.uint32)[reg], int(new[-1]) + 1 + end
-
-
-def _to_dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32).copy()).to("cuda:0")
-
-
-def _guarded(count):
-    import torch
-    return torch.full((count + GUARD,), FILL - (1 << 32), dtype=torch.int32, device="cuda:0")
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint32)
+_guarded = functools.partial(guarded, guard=GUARD, fill=FILL)
 
 
 def _run(gpu, reg, R, pixels, want=ARRAYS, stream=None):
@@ -152,7 +42,7 @@ def _run(gpu, reg, R, pixels, want=ARRAYS, stream=None):
     import torch
     h, w = reg.shape
     n = w * h
-    t_reg, t_px = _to_dev(reg.reshape(-1)), _to_dev(pixels)
+    t_reg, t_px = to_dev(reg.reshape(-1)), to_dev(pixels)
     t = {"offsets": _guarded(R + 1)}
     t.update({k: _guarded(n) for k in want})
     if stream is not None:   # (the tensors above were filled on the current stream)
@@ -161,23 +51,18 @@ def _run(gpu, reg, R, pixels, want=ARRAYS, stream=None):
                              t_pixels=t_px if "colors" in want else None, t_colors=t.get("colors"), stream=stream)
     out = {}
     for k, v in t.items():
-        a = _host(v)
-        size = R + 1 if k == "offsets" else n
-        assert (a[size:] == FILL).all(), "guard words of %s" % k
-        out[k] = a[:size]
+        out[k] = body(v, R + 1 if k == "offsets" else n, GUARD, FILL, k)
     return out
 
 
 def _same(got, want, keys=("offsets",) + ARRAYS):
     assert sorted(got) == sorted(keys)
-    for k in keys:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
-        assert np.array_equal(got[k], want[k]), k
+    same(got, want, keys)
 
 
 def _check(gpu, name):
-    reg, R = _map(name)
-    px = _frame(reg.shape[1], reg.shape[0])
+    reg, R = pixels_map(name)
+    px = frame(reg.shape[1], reg.shape[0])
     _same(_run(gpu, reg, R, px), lists_model(reg, R, px))
 
 
@@ -204,7 +89,7 @@ def test_one_id_many_times_in_a_row(gpu, name):
 # 4. Extremes of R.
 @pytest.mark.parametrize("name", ["one", "each", "line", "column"])
 def test_extremes_of_the_region_count(gpu, name):
-    reg, R = _map(name)
+    reg, R = pixels_map(name)
     assert name != "each" or R == reg.size
     _check(gpu, name)
 
@@ -212,9 +97,9 @@ def test_extremes_of_the_region_count(gpu, name):
 # 5. Ids without a pixel.
 @pytest.mark.parametrize("gaps", [(3, 0, 0), (0, 2, 0), (0, 0, 5), (2, 1, 1030)], ids=str)
 def test_ids_without_pixels_have_empty_ranges(gpu, gaps):
-    base, _ = _map("noise64x48")
-    reg, R = _with_gaps(base, *gaps)
-    px = _frame(64, 48)
+    base, _ = pixels_map("noise64x48")
+    reg, R = with_gaps(base, *gaps)
+    px = frame(64, 48)
     want = lists_model(reg, R, px)
     got = _run(gpu, reg, R, px)
     _same(got, want)
@@ -230,7 +115,7 @@ def test_a_map_with_too_many_rows_is_refused_and_nothing_is_written(gpu):
     reg = np.full((h, w), 4, np.uint32)
     reg[0] = reg[63] = np.arange(4)
     assert rows_total(reg) == 4 * 64 + 62 == 318 > w * h
-    t_reg, t_px = _to_dev(reg.reshape(-1)), _to_dev(_frame(w, h))
+    t_reg, t_px = to_dev(reg.reshape(-1)), to_dev(frame(w, h))
     t = {k: _guarded(w * h) for k in ARRAYS}
     t["offsets"] = _guarded(R + 1)
     rc = gpu.lib().dq_hip_region_pixels_dev(0, ctypes.c_void_p(t_reg.data_ptr()), w, h, R,
@@ -240,7 +125,7 @@ def test_a_map_with_too_many_rows_is_refused_and_nothing_is_written(gpu):
                                             ctypes.c_void_p(t["colors"].data_ptr()), None)
     assert rc == -2
     for k, v in t.items():
-        assert (_host(v) == FILL).all(), k
+        assert (to_host(v) == FILL).all(), k
     with pytest.raises(gpu.RegionRowsError):
         gpu.region_pixels_device(t_reg, w, h, R, t["offsets"])
     with pytest.raises(gpu.RegionRowsError):
@@ -248,12 +133,12 @@ def test_a_map_with_too_many_rows_is_refused_and_nothing_is_written(gpu):
     cts, k_outs = np.full((R, 4), FILL, np.uint32), np.full(R, FILL, np.uint32)
     with pytest.raises(gpu.RegionRowsError):
         gpu.quant_region_map_device(t_reg, w, h, R, t_px, 4, t_out=t["index"], cts=cts, k_outs=k_outs)
-    assert (_host(t["index"]) == FILL).all() and (cts == FILL).all() and (k_outs == FILL).all()
+    assert (to_host(t["index"]) == FILL).all() and (cts == FILL).all() and (k_outs == FILL).all()
 
 
 # 7. The 1024-word chunks of both scans.
 def test_scan_chunk_boundaries(gpu):
-    reg, R = _map("noise512x300")
+    reg, R = pixels_map("noise512x300")
     assert R > 100000 and rows_total(reg) > 100000
     _check(gpu, "noise512x300")
 
@@ -261,14 +146,14 @@ def test_scan_chunk_boundaries(gpu):
 # 8. Each output pointer alone, the offsets only, all together.
 @pytest.mark.parametrize("want", [(), ("index",), ("coords",), ("colors",), ARRAYS], ids=lambda w: "+".join(w) or "offsets")
 def test_output_pointers(gpu, want):
-    reg, R = _map("noise97x41")
-    px = _frame(97, 41)
+    reg, R = pixels_map("noise97x41")
+    px = frame(97, 41)
     _same(_run(gpu, reg, R, px, want=want), lists_model(reg, R, px), keys=("offsets",) + tuple(want))
 
 
 def test_host_form(gpu):
-    reg, R = _map("noise97x41")
-    px = _frame(97, 41)
+    reg, R = pixels_map("noise97x41")
+    px = frame(97, 41)
     want = lists_model(reg, R, px)
     offsets, index, coords, colours = gpu.region_pixels(reg, pixels=px)
     _same({"offsets": offsets, "index": index, "coords": coords, "colors": colours}, want)
@@ -287,9 +172,9 @@ def test_two_streams_from_two_threads(gpu):
     def work(i):
         try:
             torch.cuda.set_device(0)
-            reg, R = _map(names[i])
+            reg, R = pixels_map(names[i])
             for _ in range(3):
-                got[i] = _run(gpu, reg, R, _frame(reg.shape[1], reg.shape[0]), stream=streams[i])
+                got[i] = _run(gpu, reg, R, frame(reg.shape[1], reg.shape[0]), stream=streams[i])
         except BaseException as e:   # noqa: B036 (reported by the test's thread)
             errors.append(e)
     threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
@@ -299,21 +184,21 @@ def test_two_streams_from_two_threads(gpu):
         th.join()
     assert not errors, errors
     for i, name in enumerate(names):
-        reg, R = _map(name)
-        _same(got[i], lists_model(reg, R, _frame(reg.shape[1], reg.shape[0])))
+        reg, R = pixels_map(name)
+        _same(got[i], lists_model(reg, R, frame(reg.shape[1], reg.shape[0])))
 
 
 # 10. The inverse.
 def test_scatter_of_a_gather_is_the_identity(gpu):
     import torch
-    reg, R = _map("noise97x41")
-    px = _frame(97, 41)
+    reg, R = pixels_map("noise97x41")
+    px = frame(97, 41)
     n = reg.size
     got = _run(gpu, reg, R, px)
     t_frame = _guarded(n)
-    gpu.scatter_coords_device(_to_dev(got["colors"]), _to_dev(got["coords"]), n, 97, t_frame)
+    gpu.scatter_coords_device(to_dev(got["colors"]), to_dev(got["coords"]), n, 97, t_frame)
     torch.cuda.synchronize()
-    a = _host(t_frame)
+    a = to_host(t_frame)
     assert np.array_equal(a[:n], px) and (a[n:] == FILL).all()
 
 
@@ -327,10 +212,10 @@ def test_scatter_matches_fancy_assignment(gpu):
     want = np.full(w * h, FILL, np.uint32)
     want[p] = values
     t_frame = _guarded(w * h)
-    gpu.scatter_coords_device(_to_dev(values), _to_dev(coords), m, w, t_frame)
-    gpu.scatter_coords_device(_to_dev(values), _to_dev(coords), 0, w, t_frame)   # (n = 0: nothing)
+    gpu.scatter_coords_device(to_dev(values), to_dev(coords), m, w, t_frame)
+    gpu.scatter_coords_device(to_dev(values), to_dev(coords), 0, w, t_frame)   # (n = 0: nothing)
     torch.cuda.synchronize()
-    a = _host(t_frame)
+    a = to_host(t_frame)
     assert np.array_equal(a[:w * h], want) and (a[w * h:] == FILL).all()
 
 
@@ -351,10 +236,10 @@ def _check_pipeline(gpu, reg, R, px, k, against_regions_call):
     off, order = lists["offsets"].astype(np.int64), lists["index"].astype(np.int64)
     t_out = _guarded(n)
     cts, k_outs = np.full((R, k), FILL, np.uint32), np.full(R, FILL, np.uint32)
-    got_cts, got_k, empty = gpu.quant_region_map_device(_to_dev(reg.reshape(-1)), w, h, R, _to_dev(px), k, t_out=t_out,
+    got_cts, got_k, empty = gpu.quant_region_map_device(to_dev(reg.reshape(-1)), w, h, R, to_dev(px), k, t_out=t_out,
                                                         cts=cts, k_outs=k_outs)
     assert got_cts is cts and got_k is k_outs and empty >= 0
-    a = _host(t_out)
+    a = to_host(t_out)
     assert (a[n:] == FILL).all()
     painted, want_painted = a[:n], np.zeros(n, np.uint32)
     for r in range(R):
@@ -368,16 +253,16 @@ def _check_pipeline(gpu, reg, R, px, k, against_regions_call):
     assert np.array_equal(painted, want_painted)
     if against_regions_call:
         present = [r for r in range(R) if off[r + 1] > off[r]]
-        t_ins = [_to_dev(lists["colors"][off[r]:off[r + 1]]) for r in present]
+        t_ins = [to_dev(lists["colors"][off[r]:off[r + 1]]) for r in present]
         t_outs = [_guarded(int(off[r + 1] - off[r])) for r in present]
         ref_cts, _ = gpu.quant_weighted_regions_device(t_ins, t_outs, k)
         for r, ct, t in zip(present, ref_cts, t_outs):
             assert np.array_equal(cts[r, :k_outs[r]], ct), r
-            assert np.array_equal(_host(t)[:-GUARD], painted[order[off[r]:off[r + 1]]]), r
+            assert np.array_equal(to_host(t)[:-GUARD], painted[order[off[r]:off[r + 1]]]), r
     # the host form and a call without a frame to paint give the same tables
     out2d, cts2, k2, empty2 = gpu.quant_region_map(reg, px, k, num_regions=R)
     assert np.array_equal(out2d.reshape(-1), painted) and empty2 == empty
-    cts3, k3, _ = gpu.quant_region_map_device(_to_dev(reg.reshape(-1)), w, h, R, _to_dev(px), k)
+    cts3, k3, _ = gpu.quant_region_map_device(to_dev(reg.reshape(-1)), w, h, R, to_dev(px), k)
     for r in range(R):
         assert k2[r] == k_outs[r] == k3[r]
         assert np.array_equal(cts2[r, :k2[r]], cts[r, :k2[r]]) and np.array_equal(cts3[r, :k2[r]], cts[r, :k2[r]])
@@ -398,16 +283,16 @@ def test_pipeline_on_a_crop_of_batman(gpu):
 
 
 def test_pipeline_with_a_region_above_the_one_launch_limit(gpu):
-    reg, R = _map("big")
-    px = _frame(512, 300).copy()
+    reg, R = pixels_map("big")
+    px = frame(512, 300).copy()
     px[reg.reshape(-1) == 0] &= np.uint32(0x00F0F0F0)     # (the background: 4096 colours at most)
     _check_pipeline(gpu, reg, R, px, 4, against_regions_call=False)
 
 
 def test_pipeline_with_ids_without_pixels(gpu):
-    base, _ = _map("noise64x48")
-    reg, R = _with_gaps(base, 2, 1, 7)
-    k_outs = _check_pipeline(gpu, reg, R, _frame(64, 48), 4, against_regions_call=False)
+    base, _ = pixels_map("noise64x48")
+    reg, R = with_gaps(base, 2, 1, 7)
+    k_outs = _check_pipeline(gpu, reg, R, frame(64, 48), 4, against_regions_call=False)
     present = np.zeros(R, bool)
     present[reg.reshape(-1)] = True
     assert (k_outs[~present] == 0).all() and (k_outs[present] >= 1).all() and (~present).sum() > 9

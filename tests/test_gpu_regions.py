@@ -1,14 +1,11 @@
 """GPU: connected regions of a label map (include/dq_hip.h, "connected regions").
 
-The reference is the plain raster-order flood fill below (numpy + a Python
-stack, 4- and 8-connectivity): regions are numbered in the order the raster
-scan meets their first pixel, which is the definition.  It also computes area,
-bounding box, first pixel, label and colour sums, and never uses the code
-under test.  Equality is exact everywhere: array_equal on the region map and on
-every stats array, and the region count R.
+The reference is flood_fill_regions of regions_model.py, which never uses the
+code under test.  Equality is exact everywhere: array_equal on the region map
+and on every stats array, and the region count R.
 
-A pattern is a map of small integers; the u8 / u16 / u32 label maps are that
-map sent through an injective table per width (u16: values above 255; u32:
+A pattern (region_inputs.py) is a map of small integers; the u8 / u16 / u32
+label maps are that map sent through an injective table per width (u16: values above 255; u32:
 values above 65535 that differ ONLY in the top byte), so the three widths share
 one flood fill per (pattern, connectivity) and differ only in the "label" stat.
 
@@ -24,118 +21,14 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
+from region_dev import to_dev, to_host
+from region_inputs import frame, regions_base, widen
+from regions_model import flood_fill_regions
 
 pytestmark = pytest.mark.gpu
 
 T = 64
-UNSIGNED = {1: np.uint8, 2: np.uint16, 4: np.uint32}
-SIGNED = {1: np.uint8, 2: np.int16, 4: np.int32}      # (torch storage)
 GUARD_WORD = 0xA5A5A5A5
-
-
-# ---------------------------------------------------------------------------
-# The reference.
-def flood_fill_regions(lab2d, connectivity, pixels=None):
-    """(regions2d uint32, stats) of a 2-D integer map by raster-order flood fill."""
-    lab2d = np.asarray(lab2d)
-    h, w = lab2d.shape
-    n = h * w
-    lab = lab2d.reshape(-1).tolist()
-    reg = [-1] * n
-    steps = [(-1, 0), (1, 0), (0, -1), (0, 1)]
-    if connectivity == 8:
-        steps += [(-1, -1), (-1, 1), (1, -1), (1, 1)]
-    else:
-        assert connectivity == 4
-    count = 0
-    for s in range(n):
-        if reg[s] >= 0:
-            continue
-        rid, L = count, lab[s]
-        count += 1
-        reg[s] = rid
-        stack = [s]
-        while stack:
-            i = stack.pop()
-            y, x = divmod(i, w)
-            for dy, dx in steps:
-                yy, xx = y + dy, x + dx
-                if 0 <= yy < h and 0 <= xx < w:
-                    j = yy * w + xx
-                    if reg[j] < 0 and lab[j] == L:
-                        reg[j] = rid
-                        stack.append(j)
-    reg = np.array(reg, np.int64)
-    ys, xs = np.divmod(np.arange(n, dtype=np.int64), w)
-    first = np.full(count, n, np.int64)
-    np.minimum.at(first, reg, np.arange(n, dtype=np.int64))
-    bbox = np.zeros((count, 4), np.int64)
-    bbox[:, 0], bbox[:, 1] = w, h
-    np.minimum.at(bbox[:, 0], reg, xs)
-    np.minimum.at(bbox[:, 1], reg, ys)
-    np.maximum.at(bbox[:, 2], reg, xs)
-    np.maximum.at(bbox[:, 3], reg, ys)
-    stats = {"area": np.bincount(reg, minlength=count).astype(np.uint32),
-             "bbox": bbox.astype(np.uint32),
-             "first": first.astype(np.uint32),
-             "label": lab2d.reshape(-1)[first].astype(np.uint32)}
-    if pixels is not None:
-        px = np.asarray(pixels, np.uint32).reshape(-1)
-        sums = np.zeros((count, 3), np.uint64)
-        for c, shift in enumerate((16, 8, 0)):
-            np.add.at(sums[:, c], reg, ((px >> shift) & 0xFF).astype(np.uint64))
-        stats["sums"] = sums
-    assert (np.diff(stats["first"].astype(np.int64)) > 0).all()   # numbered in raster order of the first pixel
-    return reg.astype(np.uint32).reshape(h, w), stats
-
-
-# ---------------------------------------------------------------------------
-# Patterns: (h, w) maps of small non-negative integers.
-def _noise(w, h, k, seed=0):
-    return (fx.xorshift(w * h, seed=fx.SEED + seed) % np.uint32(k)).astype(np.int64).reshape(h, w)
-
-
-def _spiral(w, h):
-    a = np.zeros((h, w), np.int64)
-    x = y = d = 0
-    a[0, 0] = 1
-    dirs = [(1, 0), (0, 1), (-1, 0), (0, -1)]
-    inside = lambda px, py: 0 <= px < w and 0 <= py < h  # noqa: E731
-    while True:
-        for _ in range(2):
-            dx, dy = dirs[d]
-            nx, ny, ax, ay = x + dx, y + dy, x + 2 * dx, y + 2 * dy
-            if inside(nx, ny) and a[ny, nx] == 0 and (not inside(ax, ay) or a[ay, ax] == 0):
-                x, y = nx, ny
-                a[y, x] = 1
-                break
-            d = (d + 1) % 4
-        else:
-            return a
-
-
-def _pattern(name, w, h):
-    ys, xs = np.mgrid[0:h, 0:w]
-    if name == "constant":
-        return np.full((h, w), 5, np.int64)
-    if name == "checker":
-        return ((xs + ys) & 1).astype(np.int64)
-    if name == "hstripes":
-        return (ys & 1).astype(np.int64)
-    if name == "vstripes":
-        return (xs & 1).astype(np.int64)
-    if name == "spiral":
-        return _spiral(w, h)
-    if name == "comb":      # teeth on the even columns, joined along the last row
-        return (((xs & 1) == 0) | (ys == h - 1)).astype(np.int64)
-    if name == "rings":
-        return ((np.maximum(abs(xs - w // 2), abs(ys - h // 2)) // 3) & 1).astype(np.int64)
-    if name == "diagonals":  # x == y passes (T-1, T-1) -> (T, T); x + y == 2T - 1 passes (T, T-1) -> (T-1, T)
-        return np.where((xs - ys) % 8 == 0, 1, np.where((xs + ys) % 8 == 7, 2, 0)).astype(np.int64)
-    if name.startswith("noise"):
-        return _noise(w, h, int(name[5:]))
-    raise KeyError(name)
-
 
 PATTERNS = ["constant", "checker", "hstripes", "vstripes", "spiral", "comb", "rings", "diagonals",
             "noise2", "noise3", "noise200"]
@@ -149,70 +42,34 @@ SHAPES = [(1, 1), (7, 1), (1, 7),
 
 
 @functools.lru_cache(maxsize=None)
-def _base(name, w, h):
-    a = _pattern(name, w, h)
-    a.setflags(write=False)
-    return a
-
-
-@functools.lru_cache(maxsize=None)
-def _frame(w, h):
-    px = fx.xorshift(w * h, seed=fx.SEED + 77)
-    px.setflags(write=False)
-    return px
-
-
-@functools.lru_cache(maxsize=None)
 def _reference(name, w, h, connectivity):
-    """The flood fill of a pattern, once (with the colour sums of _frame)."""
-    reg, st = flood_fill_regions(_base(name, w, h), connectivity, _frame(w, h))
+    """The flood fill of a pattern, once (with the colour sums of frame)."""
+    reg, st = flood_fill_regions(regions_base(name, w, h), connectivity, frame(w, h))
     for a in [reg] + list(st.values()):
         a.setflags(write=False)
     return reg, st
-
-
-def _widen(base, width):
-    """The pattern as a label map of `width` bytes through an injective table."""
-    b = base.astype(np.uint32)
-    assert b.max() < 256
-    if width == 1:
-        return b.astype(np.uint8)
-    if width == 2:
-        return (b * 257 + 300).astype(np.uint16)            # 300 .. 65535
-    return ((b << 24) | np.uint32(0x00ABCDEF)).astype(np.uint32)   # differ only in the top byte
-
-
-def _to_dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    signed = {"u1": np.uint8, "u2": np.int16, "u4": np.int32, "u8": np.int64}[a.dtype.str[1:]]
-    return torch.from_numpy(a.view(signed).copy()).to("cuda:0")
-
-
-def _to_host(t, dtype):
-    return t.cpu().numpy().view(dtype)
 
 
 def _run(gpu, lab2d, connectivity, cap=0, pixels=None, stream=None):
     """label_regions_device on fresh tensors -> (R, regions2d, stats as unsigned numpy)."""
     import torch
     h, w = lab2d.shape
-    t_lab = _to_dev(lab2d.reshape(-1))
+    t_lab = to_dev(lab2d.reshape(-1))
     t_reg = torch.full((h * w,), -1, dtype=torch.int32, device="cuda:0")
-    t_px = _to_dev(pixels) if pixels is not None else None
+    t_px = to_dev(pixels) if pixels is not None else None
     if stream is not None:   # (the tensors above were filled on the current stream)
         stream.wait_stream(torch.cuda.current_stream())
     r, st = gpu.label_regions_device(t_lab, w, h, t_reg, connectivity=connectivity, stats_capacity=cap,
                                      t_pixels=t_px, stream=stream)
-    out = {k: _to_host(v, np.uint64 if k == "sums" else np.uint32) for k, v in st.items()}
-    return r, _to_host(t_reg, np.uint32).reshape(h, w), out
+    out = {k: to_host(v, np.uint64 if k == "sums" else np.uint32) for k, v in st.items()}
+    return r, to_host(t_reg, np.uint32).reshape(h, w), out
 
 
 def _check(gpu, name, w, h, connectivity, width):
     want_reg, want = _reference(name, w, h, connectivity)
-    lab = _widen(_base(name, w, h), width)
+    lab = widen(regions_base(name, w, h), width)
     R = len(want["area"])
-    r, reg, st = _run(gpu, lab, connectivity, cap=R, pixels=_frame(w, h))
+    r, reg, st = _run(gpu, lab, connectivity, cap=R, pixels=frame(w, h))
     assert r == R
     assert np.array_equal(reg, want_reg)
     assert sorted(st) == ["area", "bbox", "first", "label", "sums"]
@@ -257,7 +114,7 @@ def test_diagonals_differ_exactly_at_the_seams(gpu):
     """The lines of "diagonals" touch only at corners, also across the tile
     corners: one region per pixel of a line with 4-connectivity, one per line
     with 8 (the reference says so; here the two answers are told apart)."""
-    base = _base("diagonals", PW, PH)
+    base = regions_base("diagonals", PW, PH)
     r4 = _reference("diagonals", PW, PH, 4)[0]
     r8 = _reference("diagonals", PW, PH, 8)[0]
     assert base[T - 1, T - 1] == base[T, T] == 1 and base[T - 1, T] == base[T, T - 1] == 2
@@ -298,8 +155,8 @@ def test_stats_capacity(gpu, which):
     R = len(want["area"])
     cap = {"zero": 0, "half": R // 2, "more": R + 5}[which]
     m = min(R, cap)
-    lab = _widen(_base("noise3", w, h), 1)
-    t_lab, t_px = _to_dev(lab.reshape(-1)), _to_dev(_frame(w, h))
+    lab = widen(regions_base("noise3", w, h), 1)
+    t_lab, t_px = to_dev(lab.reshape(-1)), to_dev(frame(w, h))
     t_reg = torch.full((w * h,), -1, dtype=torch.int32, device="cuda:0")
     guard = np.full(1, GUARD_WORD, np.uint32).view(np.int32)[0]
     per = {"area": 1, "bbox": 4, "first": 1, "label": 1, "sums": 6}   # 4-byte words per region
@@ -309,9 +166,9 @@ def test_stats_capacity(gpu, which):
                                            ptr(bufs["bbox"]), ptr(bufs["first"]), ptr(bufs["label"]), ptr(t_px),
                                            ptr(bufs["sums"]), None)
     assert r == R
-    assert np.array_equal(_to_host(t_reg, np.uint32).reshape(h, w), want_reg)
+    assert np.array_equal(to_host(t_reg, np.uint32).reshape(h, w), want_reg)
     for k, p in per.items():
-        got = _to_host(bufs[k], np.uint32)
+        got = to_host(bufs[k], np.uint32)
         assert (got[m * p:] == GUARD_WORD).all(), k
         head = got[:m * p]
         if k == "sums":
@@ -333,9 +190,9 @@ def test_two_streams_at_once(gpu):
 
     def work(i):
         name, connectivity = cases[i]
-        lab = _widen(_base(name, PW, PH), 2)
+        lab = widen(regions_base(name, PW, PH), 2)
         results[i] = _run(gpu, lab, connectivity, cap=len(_reference(name, PW, PH, connectivity)[1]["area"]),
-                          pixels=_frame(PW, PH), stream=streams[i])
+                          pixels=frame(PW, PH), stream=streams[i])
 
     for name, connectivity in cases:   # (the flood fills, before the threads start)
         _reference(name, PW, PH, connectivity)
@@ -352,10 +209,10 @@ def test_two_streams_at_once(gpu):
 
 
 def test_same_input_twice_gives_identical_bytes(gpu):
-    lab = _widen(_base("noise3", PW, PH), 1)
+    lab = widen(regions_base("noise3", PW, PH), 1)
     R = len(_reference("noise3", PW, PH, 8)[1]["area"])
-    a = _run(gpu, lab, 8, cap=R, pixels=_frame(PW, PH))
-    b = _run(gpu, lab, 8, cap=R, pixels=_frame(PW, PH))
+    a = _run(gpu, lab, 8, cap=R, pixels=frame(PW, PH))
+    b = _run(gpu, lab, 8, cap=R, pixels=frame(PW, PH))
     assert a[0] == b[0] and a[1].tobytes() == b[1].tobytes()
     for k in a[2]:
         assert a[2][k].tobytes() == b[2][k].tobytes(), k
@@ -368,14 +225,14 @@ def test_pointers_offset_by_one_element(gpu, width):
     import torch
     w, h, connectivity = T + 3, T + 2, 8
     want_reg, want = _reference("noise3", w, h, connectivity)
-    lab = _widen(_base("noise3", w, h), width).reshape(-1)
+    lab = widen(regions_base("noise3", w, h), width).reshape(-1)
     room = torch.zeros(w * h + 1, dtype={1: torch.uint8, 2: torch.int16, 4: torch.int32}[width], device="cuda:0")
-    room[1:] = _to_dev(lab)
+    room[1:] = to_dev(lab)
     t_lab = room[1:]
     t_reg = torch.full((w * h + 1,), -1, dtype=torch.int32, device="cuda:0")
     assert t_lab.is_contiguous() and t_lab.data_ptr() % (4 if width < 4 else 16) == width
     r, st = gpu.label_regions_device(t_lab, w, h, t_reg[1:], connectivity=connectivity, stats_capacity=4)
-    got = _to_host(t_reg, np.uint32)
+    got = to_host(t_reg, np.uint32)
     assert r == len(want["area"]) and got[0] == 0xFFFFFFFF
     assert np.array_equal(got[1:].reshape(h, w), want_reg)
-    assert np.array_equal(_to_host(st["area"], np.uint32), want["area"][:4])
+    assert np.array_equal(to_host(st["area"], np.uint32), want["area"][:4])

@@ -18,9 +18,9 @@ A with three labels and B with 200, and area arrays of 4 * 2^20 + 1025
 regions) and asserts that each is past the threshold it is here for.
 
 The references are the stage suites' own models, taken by import and run once
-per session (lru_cache): the flood fill of test_gpu_regions, adjacency_model,
-merge_model and stats_model, lists_model, containment_model.model and
-size_order.  Equality is exact: array_equal on every output array, == on every
+per session (lru_cache): flood_fill_regions and stats_model (regions_model.py),
+adjacency_model, merge_model, lists_model (pixels_model.py),
+containment_model.model and size_order.  Equality is exact: array_equal on every output array, == on every
 count.  The tensors a test hands to a call (region maps, offsets and lists)
 are 8 words longer than needed and filled with a guard word that must still be
 there afterwards; the stats, graph and tree tensors are allocated by the
@@ -37,10 +37,11 @@ import pytest
 
 import containment_model as cm
 import test_regions_atsize_inputs as inp
-from test_gpu_containment import ARRAYS
-from test_gpu_merge import merge_model, stats_model
-from test_gpu_pixels import _permuted, lists_model
-from test_gpu_regions import _widen
+from merge_model import merge_model
+from pixels_model import lists_model
+from region_dev import body, guarded, to_dev
+from region_inputs import permuted as permuted_ids, widen
+from regions_model import stats_model
 
 pytestmark = pytest.mark.gpu
 
@@ -48,32 +49,16 @@ W, H, N, CONN = inp.W, inp.H, inp.N, inp.CONN
 GUARD = 8
 FILL = 0xA5A5A5A5
 U64 = ("sums", "step", "enclosed")       # the 8-byte arrays
-
-
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    signed = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}[a.dtype.itemsize]
-    return torch.from_numpy(a.view(signed).copy()).to("cuda:0")
+ARRAYS = cm.ARRAYS
+_guarded = functools.partial(guarded, guard=GUARD, fill=FILL)
 
 
 def _host(t, key=None):
     return t.cpu().numpy().view(np.uint64 if key in U64 else np.uint32)
 
 
-def _guarded(count):
-    import torch
-    return torch.full((count + GUARD,), FILL - (1 << 32), dtype=torch.int32, device="cuda:0")
-
-
-def _body(t, count, what):
-    """The first `count` words of a guarded tensor; the guard behind them is intact."""
-    a = _host(t)
-    assert a.size == count + GUARD and (a[count:] == FILL).all(), "guard words of %s" % what
-    return a[:count]
-
-
 def _same(got, want, keys):
+    """region_dev.same, and at these sizes how many words differ and where."""
     for k in keys:
         assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
         g, w = got[k].reshape(-1), want[k].reshape(-1)
@@ -99,12 +84,12 @@ def _device_part(what):
 def test_regions(gpu, name, width, connectivity):
     want_reg, want = inp.regions(name, connectivity)
     R = len(want["area"])
-    lab = _widen(inp.labels(name), width)
+    lab = widen(inp.labels(name), width)
     with _device_part("regions %s u%d conn %d" % (name, 8 * width, connectivity)):
         t_reg = _guarded(N)
-        r, st = gpu.label_regions_device(_dev(lab.reshape(-1)), W, H, t_reg, connectivity=connectivity,
-                                         stats_capacity=R, t_pixels=_dev(inp.frame()))
-        reg = _body(t_reg, N, "regions")
+        r, st = gpu.label_regions_device(to_dev(lab.reshape(-1)), W, H, t_reg, connectivity=connectivity,
+                                         stats_capacity=R, t_pixels=to_dev(inp.frame()))
+        reg = body(t_reg, N, GUARD, FILL, "regions")
         got = {k: _host(v, k) for k, v in st.items()}
     assert r == R, "R = %d, the flood fill has %d" % (r, R)
     bad = np.flatnonzero(reg != want_reg.reshape(-1))
@@ -122,7 +107,7 @@ def test_adjacency(gpu, name):
     want, R = inp.graph(name), inp.count(name)
     E = want["E"]
     with _device_part("adjacency %s" % name):
-        t_reg, t_px = _dev(inp.regions(name)[0].reshape(-1)), _dev(inp.frame())
+        t_reg, t_px = to_dev(inp.regions(name)[0].reshape(-1)), to_dev(inp.frame())
         e0, g0 = gpu.region_adjacency_device(t_reg, W, H, connectivity=CONN)
         e, g = gpu.region_adjacency_device(t_reg, W, H, connectivity=CONN, edge_capacity=E, t_pixels=t_px,
                                            num_regions=R)
@@ -157,16 +142,16 @@ def test_merge(gpu, name, min_area, in_place):
     assert 1 < want["R"] < R and want["rounds"] >= 1
     with _device_part("merge %s min_area %d %s" % (name, min_area, "in place" if in_place else "apart")):
         t_in = _guarded(N)
-        t_in[:N] = _dev(reg.reshape(-1))
+        t_in[:N] = to_dev(reg.reshape(-1))
         t_out = t_in if in_place else _guarded(N)
-        t = {k: _dev(st[k].reshape(-1)) for k in ("area", "first", "sums", "bbox")}
-        r, rounds, out = gpu.merge_regions_device(t_in, R, t["area"], t["first"], t["sums"], _dev(edges.reshape(-1)),
+        t = {k: to_dev(st[k].reshape(-1)) for k in ("area", "first", "sums", "bbox")}
+        r, rounds, out = gpu.merge_regions_device(t_in, R, t["area"], t["first"], t["sums"], to_dev(edges.reshape(-1)),
                                                   min_area, t_bbox=t["bbox"], num_edges=len(edges),
                                                   t_out_regions=None if in_place else t_out, stats_capacity=R, n=N)
         assert out["regions"] is t_out
         got = {k: _host(v, k) for k, v in out.items() if k != "regions"}
-        got["regions"] = _body(t_out, N, "the output map")
-        kept = None if in_place else _body(t_in, N, "the input map")
+        got["regions"] = body(t_out, N, GUARD, FILL, "the output map")
+        kept = None if in_place else body(t_in, N, GUARD, FILL, "the input map")
     assert (r, rounds) == (want["R"], want["rounds"]), "R' = %d in %d rounds, the model: %d in %d" % (
         r, rounds, want["R"], want["rounds"])
     assert kept is None or np.array_equal(kept, reg.reshape(-1))
@@ -181,7 +166,7 @@ def test_merge(gpu, name, min_area, in_place):
 def _region_map(name, permuted):
     reg = inp.regions(name)[0]
     if permuted:
-        reg = _permuted(reg, 5)
+        reg = permuted_ids(reg, 5)
         reg.setflags(write=False)
     return reg
 
@@ -196,7 +181,7 @@ def _pixel_lists(gpu, t_reg, R, t_px):
     t = {"offsets": _guarded(R + 1), "index": _guarded(N), "coords": _guarded(N), "colors": _guarded(N)}
     gpu.region_pixels_device(t_reg, W, H, R, t["offsets"], t_coords=t["coords"], t_index=t["index"], t_pixels=t_px,
                              t_colors=t["colors"])
-    return {k: _body(v, R + 1 if k == "offsets" else N, k) for k, v in t.items()}
+    return {k: body(v, R + 1 if k == "offsets" else N, GUARD, FILL, k) for k, v in t.items()}
 
 
 @pytest.mark.parametrize("permuted", [False, True], ids=["raster_ids", "permuted_ids"])
@@ -205,7 +190,7 @@ def test_pixels(gpu, permuted):
     reg, want = _region_map("B", permuted), _lists("B", permuted)
     assert permuted == (not np.array_equal(reg, inp.regions("B")[0]))
     with _device_part("pixels B%s" % (" permuted" if permuted else "")):
-        got = _pixel_lists(gpu, _dev(reg.reshape(-1)), R, _dev(inp.frame()))
+        got = _pixel_lists(gpu, to_dev(reg.reshape(-1)), R, to_dev(inp.frame()))
     assert got["offsets"][R] == N
     _same(got, want, ("offsets", "index", "coords", "colors"))
 
@@ -230,8 +215,8 @@ def test_containment(gpu, name):
     want, R = inp.tree(name), inp.count(name)
     assert want["levels"] >= 2 and want["reached"] == R
     with _device_part("containment %s" % name):
-        out, counts = _containment(gpu, _dev(inp.regions(name)[0].reshape(-1)), R, _dev(inp.regions(name)[1]["area"]),
-                                   _dev(inp.graph(name)["edges"]))
+        out, counts = _containment(gpu, to_dev(inp.regions(name)[0].reshape(-1)), R,
+                                   to_dev(inp.regions(name)[1]["area"]), to_dev(inp.graph(name)["edges"]))
     _same_tree(out, counts, want)
 
 
@@ -245,9 +230,9 @@ def test_containment_of_b_with_the_edges_shuffled_and_a_third_doubled(gpu):
     mixed[swap] = mixed[swap][:, ::-1]
     assert len(mixed) > len(edges) + len(edges) // 4
     with _device_part("containment B twice"):
-        t_reg, t_area = _dev(inp.regions("B")[0].reshape(-1)), _dev(inp.regions("B")[1]["area"])
-        out, counts = _containment(gpu, t_reg, R, t_area, _dev(edges))
-        out2, counts2 = _containment(gpu, t_reg, R, t_area, _dev(mixed))
+        t_reg, t_area = to_dev(inp.regions("B")[0].reshape(-1)), to_dev(inp.regions("B")[1]["area"])
+        out, counts = _containment(gpu, t_reg, R, t_area, to_dev(edges))
+        out2, counts2 = _containment(gpu, t_reg, R, t_area, to_dev(mixed))
         equal = {k: torch.equal(out[k], out2[k]) for k in ARRAYS}
     assert counts2 == counts
     assert all(equal.values()), equal
@@ -279,7 +264,7 @@ def test_regions_by_size(gpu, pattern):
     area, want_order, want_rank = _areas(pattern)
     assert pattern != "random_2^32" or int(area.max()) >= 1 << 24
     with _device_part("size order %s" % pattern):
-        order, rank = gpu.regions_by_size_device(_dev(area))
+        order, rank = gpu.regions_by_size_device(to_dev(area))
         got = {"order": _host(order), "rank": _host(rank)}
     _same(got, {"order": want_order, "rank": want_rank}, ("order", "rank"))
     if pattern == "equal":
@@ -289,20 +274,20 @@ def test_regions_by_size(gpu, pattern):
 # ---------------------------------------------------------------------------
 # 7. The chain on A, each stage on the device output of the one before.
 def test_chain_on_the_device(gpu):
-    lab = _widen(inp.labels("A"), 1)
+    lab = widen(inp.labels("A"), 1)
     want_reg, want_stats = inp.regions("A")
     R, E = inp.count("A"), inp.graph("A")["E"]
     with _device_part("chain A"):
-        t_px = _dev(inp.frame())
+        t_px = to_dev(inp.frame())
         t_reg = _guarded(N)
-        r, st = gpu.label_regions_device(_dev(lab.reshape(-1)), W, H, t_reg, connectivity=CONN, stats_capacity=N,
+        r, st = gpu.label_regions_device(to_dev(lab.reshape(-1)), W, H, t_reg, connectivity=CONN, stats_capacity=N,
                                          t_pixels=t_px)
         e0, _ = gpu.region_adjacency_device(t_reg, W, H, connectivity=CONN)
         e, g = gpu.region_adjacency_device(t_reg, W, H, connectivity=CONN, edge_capacity=e0, t_pixels=t_px,
                                            num_regions=r)
         out, counts = _containment(gpu, t_reg, r, st["area"], g["edges"])
         lists = _pixel_lists(gpu, t_reg, r, t_px)
-        reg = _body(t_reg, N, "regions")
+        reg = body(t_reg, N, GUARD, FILL, "regions")
     assert (r, e0, e) == (R, E, E)
     assert np.array_equal(reg, want_reg.reshape(-1))
     _same({k: _host(v, k) for k, v in st.items()}, want_stats, ("area", "bbox", "first", "sums"))

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import skeleton_model as sm
+from region_dev import to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -33,22 +34,14 @@ SHAPES = [(s, o) for s in SIDES for o in (5, 67)] + [(o, s) for s in SIDES for o
 DTYPES = {"skel": np.uint8, "when": np.uint16}
 
 
-def _dev(a):
-    import torch
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).to("cuda:0")
-
-
 def _host(name, t):
     return t.cpu().numpy().view(DTYPES.get(name, np.uint32))
 
 
 def skeleton(gpu, reg, nreg, max_iters=0, outputs=None, stream=None):
     h, w = reg.shape
-    kept, out = gpu.region_skeleton_device(_dev(reg.astype(np.uint32)), w, h, nreg, max_iters=max_iters, outputs=outputs,
-                                           stream=stream)
+    kept, out = gpu.region_skeleton_device(to_dev(reg.astype(np.uint32)), w, h, nreg, max_iters=max_iters,
+                                           outputs=outputs, stream=stream)
     got = {k: (_host(k, v) if k in ARRAYS else v) for k, v in out.items()}
     got["kept"] = kept
     return got
@@ -270,7 +263,7 @@ def three_shapes():
     return reg, sm.region_skeleton(reg, 4)
 
 
-def _guarded(nbytes):
+def _guarded(nbytes):   # (bytes, not region_dev's words: the outputs here are u8, u16 and u32)
     import torch
     return torch.full((nbytes + 64,), GUARD, dtype=torch.uint8, device="cuda:0")
 
@@ -279,7 +272,7 @@ def _raw(gpu, reg, nreg, skip, words=True):
     import torch
     h, w = reg.shape
     size = {"skel": h * w, "skeled": 4 * h * w, "when": 2 * h * w}
-    t_reg = _dev(reg)
+    t_reg = to_dev(reg)
     t = {k: _guarded(size.get(k, 4 * nreg)) for k in ARRAYS if k not in skip}
     p = lambda k: ctypes.c_void_p(t[k].data_ptr()) if k in t else None  # noqa: E731
     its, conv = ctypes.c_uint32(77), ctypes.c_uint32(77)
@@ -314,7 +307,7 @@ def test_the_host_words_may_be_null(gpu):
 
 def test_skeled_in_place(gpu):
     reg, want = three_shapes()
-    t_reg = _dev(reg)
+    t_reg = to_dev(reg)
     kept, out = gpu.region_skeleton_device(t_reg, reg.shape[1], reg.shape[0], 4, outputs=("skeled", "thick"),
                                            t_skeled=t_reg)
     assert kept == want["kept"] and out["skeled"] is t_reg

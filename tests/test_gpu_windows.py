@@ -1,16 +1,11 @@
 """GPU: the capture windows of a region map (include/dq_hip.h, "capture
 windows") and the region map -> windows -> per-window quant pipeline.
 
-The reference is the numpy model below, written from the definition alone and
-using none of the code under test: per region a boolean grid of the blocks it
-has a pixel in, `expand` shift-and-or dilations by the plus-shaped cross, then
-the blocks of the window in raster order and in each block its pixels in
-raster order, without the pixels outside the frame and the masked ones.  (The
-reference application needs OpenCV, which is not available to the tests: the
-model is the oracle, as in the adjacency, merge and pixel-list stages.)  The
-pipeline is checked against the CPU oracle's weighted quant_recurse on each
-window's colours in list order, and against quant_weighted_regions_device on
-the same ranges.  Equality is exact everywhere: array_equal on every array, ==
+The reference is windows_model of windows_model.py, written from the definition
+alone and using none of the code under test; the maps, masks and the CASES the
+tests run are in region_inputs.py.  The pipeline is checked against the CPU
+oracle's weighted quant_recurse on each window's colours in list order, and
+against quant_weighted_regions_device on the same ranges.  Equality is exact everywhere: array_equal on every array, ==
 on every scalar.  Every output buffer carries guard words behind its last entry.
 
 Shapes are the smallest at which each mechanism can fail: maps smaller than a
@@ -28,198 +23,34 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
-from test_gpu_merge import _frame
-from test_gpu_pixels import _map as _pixels_map
+from region_dev import body, guarded, same, to_dev, to_host
+from region_inputs import CASES, frame, mask_of, wmap
+from windows_model import dilate_square, window_grids, windows_model
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 8
 FILL = 0xA5A5A5A5
 ARRAYS = ("index", "coords", "colors")
+_guarded = functools.partial(guarded, guard=GUARD, fill=FILL)
 
 
 # ---------------------------------------------------------------------------
-# The reference.
-def dilate_cross(grid):
-    """One dilation by the 3 x 3 cross; nothing comes in from outside the grid."""
-    out = grid.copy()
-    out[1:, :] |= grid[:-1, :]
-    out[:-1, :] |= grid[1:, :]
-    out[:, 1:] |= grid[:, :-1]
-    out[:, :-1] |= grid[:, 1:]
-    return out
-
-
-def dilate_square(grid):
-    """One dilation by the full 3 x 3 square (what the element is NOT)."""
-    rows = grid.copy()
-    rows[1:, :] |= grid[:-1, :]
-    rows[:-1, :] |= grid[1:, :]
-    out = rows.copy()
-    out[:, 1:] |= rows[:, :-1]
-    out[:, :-1] |= rows[:, 1:]
-    return out
-
-
-def own_blocks(reg2d, R, d):
-    """Per id < R the (block row, block column) arrays of the blocks it has a pixel in."""
-    h, w = reg2d.shape
-    bw = -(-w // d)
-    ys, xs = np.mgrid[0:h, 0:w]
-    ids = reg2d.reshape(-1).astype(np.int64)
-    blocks = ((ys // d) * bw + xs // d).reshape(-1)
-    keep = ids < R
-    pairs = np.unique(ids[keep] * (1 << 32) + blocks[keep])
-    owner, block = pairs >> 32, pairs & 0xFFFFFFFF
-    starts = np.searchsorted(owner, np.arange(R + 1))
-    return [(block[starts[r]:starts[r + 1]] // bw, block[starts[r]:starts[r + 1]] % bw) for r in range(R)]
-
-
-def window_grids(reg2d, R, d, e, area=None, min_area=0, dilate=dilate_cross, bbox=False):
-    """Yields (r, j_lo, i_lo, boolean grid of window(r) from block (j_lo, i_lo)) for every region with a
-    window.  bbox: the grid is cut to the own blocks' bounding box grown by e (all else is False anyway)."""
-    h, w = reg2d.shape
-    bh, bw = -(-h // d), -(-w // d)
-    for r, (bj, bi) in enumerate(own_blocks(reg2d, R, d)):
-        if len(bj) == 0 or (area is not None and area[r] <= min_area):
-            continue
-        j0, j1, i0, i1 = 0, bh, 0, bw
-        if bbox:
-            j0, j1 = max(int(bj.min()) - e, 0), min(int(bj.max()) + e + 1, bh)
-            i0, i1 = max(int(bi.min()) - e, 0), min(int(bi.max()) + e + 1, bw)
-        grid = np.zeros((j1 - j0, i1 - i0), bool)
-        grid[bj - j0, bi - i0] = True
-        for _ in range(e):
-            grid = dilate(grid)
-        yield r, j0, i0, grid
-
-
-def block_pixels(h, w, d, mask=None):
-    """Per block (raster order of blocks) its surviving pixel indexes in raster order."""
-    bh, bw = -(-h // d), -(-w // d)
-    alive = np.ones(h * w, bool) if mask is None else np.asarray(mask).reshape(-1) == 0
-    out = []
-    for j in range(bh):
-        for i in range(bw):
-            ys, xs = np.mgrid[j * d:min(j * d + d, h), i * d:min(i * d + d, w)]
-            p = (ys * w + xs).reshape(-1)
-            out.append(p[alive[p]])
-    return out
-
-
-def windows_model(reg2d, R, pixels, d, e, mask=None, area=None, min_area=0, lists=True, bbox=False):
-    """The outputs of the definition, and P and T' of the refusal rule."""
-    reg2d = np.asarray(reg2d)
-    h, w = reg2d.shape
-    bw = -(-w // d)
-    per_block = block_pixels(h, w, d, mask)
-    m = np.array([len(p) for p in per_block], np.int64)
-    lengths, chunks, P, T = np.zeros(R, np.int64), [], 0, 0
-    for r, j0, i0, grid in window_grids(reg2d, R, d, e, area, min_area, bbox=bbox):
-        js, is_ = np.nonzero(grid)                       # (raster order of blocks)
-        blocks = (js + j0) * bw + is_ + i0
-        P += len(blocks)
-        T += int(js.max() - js.min() + 1)
-        lengths[r] = m[blocks].sum()
-        if lists:
-            chunks.extend(per_block[b] for b in blocks)
-    offsets = np.concatenate([[0], np.cumsum(lengths)])
-    assert offsets[-1] <= (1 << 32) - 1
-    out = {"offsets": offsets.astype(np.uint32), "P": P, "T": T}
-    if lists:
-        order = np.concatenate(chunks).astype(np.int64) if chunks else np.zeros(0, np.int64)
-        out.update(index=order.astype(np.uint32), coords=((order % w) | (order // w) << 16).astype(np.uint32),
-                   colors=np.asarray(pixels, np.uint32).reshape(-1)[order])
-    for v in out.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return out
-
-
-# ---------------------------------------------------------------------------
-# Inputs.
-def _islands(h, w, places):
-    reg = np.zeros((h, w), np.uint32)
-    for i, (x, y) in enumerate(places):
-        reg[y:y + 3, x:x + 3] = 1 + i
-    return reg
-
-
-@functools.lru_cache(maxsize=None)
-def wmap(name):
-    """(region ids (H, W) uint32, R) of a named case; the names of test_gpu_pixels.py pass through."""
-    if name == "diagonal":            # a one-pixel-wide line of id 1 on a background of id 0
-        reg = np.eye(40, dtype=np.uint32)
-    elif name == "islands":           # 3 x 3 islands in the four corners and the middle, and a pair whose
-        reg = _islands(48, 64, [(0, 0), (61, 0), (0, 45), (61, 45), (29, 21), (10, 30), (22, 30)])   # windows overlap
-    elif name == "each16x12":         # one region per pixel
-        reg = np.arange(16 * 12, dtype=np.uint32).reshape(12, 16)
-    elif name == "refused":           # id 0 in the first and the last block, id 1 between: T' = 98 > P = 50
-        reg = np.ones((200, 4), np.uint32)
-        reg[0:4] = reg[196:200] = 0
-    else:
-        return _pixels_map(name)
-    reg = np.ascontiguousarray(reg, np.uint32)
-    reg.setflags(write=False)
-    return reg, int(reg.max()) + 1
-
-
-def mask_of(kind, h, w):
-    if kind is None:
-        return None
-    mask = np.zeros((h, w), np.uint8)
-    if kind == "random":              # about 30 %
-        mask = (fx.xorshift(h * w, seed=fx.SEED + 31) % np.uint32(10) < 3).astype(np.uint8).reshape(h, w)
-        assert 0.25 < mask.mean() < 0.35
-    elif kind == "block":             # one whole block: m(b) = 0
-        mask[8:12, 20:24] = 1
-    elif kind == "island-window":     # the whole window of the island at the top left corner of "islands"
-        mask[0:12, 0:12] = 7
-    else:
-        raise KeyError(kind)
-    mask.setflags(write=False)
-    return mask
-
-
-# every (map, d, e) the tests below run, for the CPU check that T' <= P
-CASES = ([("rows65", 1, 0), ("comb", 1, 0), ("noise97x41", 4, 2), ("rows3x5", 4, 2), ("rows1x7", 4, 2),
-          ("rows64", 4, 2), ("one", 4, 2), ("diagonal", 4, 1), ("diagonal", 4, 2), ("islands", 4, 2),
-          ("each16x12", 4, 2), ("each16x12", 8, 3), ("each16x12", 2, 0), ("noise64x48", 4, 2), ("big", 4, 2),
-          ("noise97x41-permuted", 4, 2)] +
-         [(name, d, e) for name in ("noise96x80", "noise96x80-permuted") for d, e in ((2, 1), (4, 0), (4, 2), (8, 3))])
-
-
-# ---------------------------------------------------------------------------
-def _to_dev(a, dtype=np.uint32):
-    import torch
-    a = np.ascontiguousarray(a, dtype)
-    return torch.from_numpy(a.view(np.int32 if dtype == np.uint32 else np.uint8).copy()).to("cuda:0")
-
-
-def _guarded(count):
-    import torch
-    return torch.full((count + GUARD,), FILL - (1 << 32), dtype=torch.int32, device="cuda:0")
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
 def _run(gpu, reg, R, px, d, e, mask=None, area=None, min_area=0, want=ARRAYS, stream=None, total=None):
     """region_windows_device on fresh guarded tensors: the count-only call (unless `total` is given),
     then the call with room -> dict of the arrays asked for, the offsets and M."""
     import torch
     h, w = reg.shape
-    t_reg, t_px = _to_dev(reg.reshape(-1)), _to_dev(px)
-    t_mask = _to_dev(mask.reshape(-1), np.uint8) if mask is not None else None
-    t_area = _to_dev(area) if area is not None else None
+    t_reg, t_px = to_dev(reg.reshape(-1)), to_dev(px)
+    t_mask = to_dev(mask.reshape(-1), np.uint8) if mask is not None else None
+    t_area = to_dev(area) if area is not None else None
     if stream is not None:   # (the tensors above were filled on the current stream)
         stream.wait_stream(torch.cuda.current_stream())
     kw = dict(block=d, expand=e, t_mask=t_mask, t_area=t_area, min_area=min_area, stream=stream)
     if total is None:
         t_off = _guarded(R + 1)
         total = gpu.region_windows_device(t_reg, w, h, R, t_off, **kw)
-        a = _host(t_off)
+        a = to_host(t_off)
         assert (a[R + 1:] == FILL).all() and a[R] == total
     t = {"offsets": _guarded(R + 1)}
     t.update({k: _guarded(total) for k in want})
@@ -231,24 +62,19 @@ def _run(gpu, reg, R, px, d, e, mask=None, area=None, min_area=0, want=ARRAYS, s
     assert got == total
     out = {"M": total}
     for k, v in t.items():
-        a = _host(v)
-        size = R + 1 if k == "offsets" else total
-        assert (a[size:] == FILL).all(), "guard words of %s" % k
-        out[k] = a[:size]
+        out[k] = body(v, R + 1 if k == "offsets" else total, GUARD, FILL, k)
     return out
 
 
 def _same(got, want, keys=("offsets",) + ARRAYS):
     assert got["M"] == int(want["offsets"][-1])
-    for k in keys:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
-        assert np.array_equal(got[k], want[k]), k
+    same(got, want, keys)
 
 
 def _check(gpu, name, d, e, mask=None, area=None, min_area=0):
     reg, R = wmap(name)
     assert (name, d, e) in CASES
-    px = _frame(reg.shape[1], reg.shape[0])
+    px = frame(reg.shape[1], reg.shape[0])
     want = windows_model(reg, R, px, d, e, mask, area, min_area)
     got = _run(gpu, reg, R, px, d, e, mask, area, min_area)
     _same(got, want)
@@ -265,12 +91,12 @@ def test_block_one_expand_zero_is_the_pixel_lists(gpu, name):
     h, w = reg.shape
     t = {k: _guarded(w * h) for k in ARRAYS}
     t_off = _guarded(R + 1)
-    gpu.region_pixels_device(_to_dev(reg.reshape(-1)), w, h, R, t_off, t_coords=t["coords"], t_index=t["index"],
-                             t_pixels=_to_dev(_frame(w, h)), t_colors=t["colors"])
+    gpu.region_pixels_device(to_dev(reg.reshape(-1)), w, h, R, t_off, t_coords=t["coords"], t_index=t["index"],
+                             t_pixels=to_dev(frame(w, h)), t_colors=t["colors"])
     torch.cuda.synchronize()
-    assert got["M"] == w * h and np.array_equal(got["offsets"], _host(t_off)[:R + 1])
+    assert got["M"] == w * h and np.array_equal(got["offsets"], to_host(t_off)[:R + 1])
     for k in ARRAYS:
-        assert np.array_equal(got[k], _host(t[k])[:w * h]), k
+        assert np.array_equal(got[k], to_host(t[k])[:w * h]), k
 
 
 # 2. Clipped right and bottom blocks, maps smaller than a block, one block row, one region.
@@ -329,7 +155,7 @@ def test_mask(gpu, name, kind):
     if kind == "island-window":       # its list is empty, its neighbours' lists are not
         assert lengths[1] == 0 and (lengths[[0, 2, 3, 4, 5, 6, 7]] > 0).all()
     else:
-        assert got["M"] < int(windows_model(reg, R, _frame(64, 48), 4, 2)["offsets"][-1])
+        assert got["M"] < int(windows_model(reg, R, frame(64, 48), 4, 2)["offsets"][-1])
 
 
 # 8. The area rule.
@@ -348,7 +174,7 @@ def test_area_rule(gpu):
 # 8b. Ids >= R found no block and have no list; their pixels are pixels of the frame like any other.
 def test_ids_at_or_above_the_region_count_are_skipped(gpu):
     reg, R = wmap("noise97x41")
-    px = _frame(97, 41)
+    px = frame(97, 41)
     want = windows_model(reg, R - 40, px, 4, 2)
     got = _run(gpu, reg, R - 40, px, 4, 2)
     _same(got, want)
@@ -364,20 +190,20 @@ def test_capacity_one_short(gpu):
     M = int(want["offsets"][-1])
     t = {k: _guarded(M) for k in ARRAYS}
     t_off = _guarded(R + 1)
-    got = gpu.region_windows_device(_to_dev(reg.reshape(-1)), w, h, R, t_off, capacity=M - 1, t_coords=t["coords"],
-                                    t_index=t["index"], t_pixels=_to_dev(_frame(w, h)), t_colors=t["colors"])
+    got = gpu.region_windows_device(to_dev(reg.reshape(-1)), w, h, R, t_off, capacity=M - 1, t_coords=t["coords"],
+                                    t_index=t["index"], t_pixels=to_dev(frame(w, h)), t_colors=t["colors"])
     assert got == M
-    a = _host(t_off)
+    a = to_host(t_off)
     assert np.array_equal(a[:R + 1], want["offsets"]) and (a[R + 1:] == FILL).all()
     for k in ARRAYS:
-        assert (_host(t[k]) == FILL).all(), k
+        assert (to_host(t[k]) == FILL).all(), k
 
 
 # 10. The count alone, each list array alone, all three.
 @pytest.mark.parametrize("want", [(), ("index",), ("coords",), ("colors",), ARRAYS], ids=lambda w: "+".join(w) or "count")
 def test_output_combinations(gpu, want):
     reg, R = wmap("noise97x41")
-    px = _frame(97, 41)
+    px = frame(97, 41)
     _same(_run(gpu, reg, R, px, 4, 2, want=want), windows_model(reg, R, px, 4, 2), keys=("offsets",) + tuple(want))
 
 
@@ -387,8 +213,8 @@ def test_scan_chunks(gpu):
     want = windows_model(reg, R, None, 4, 2, lists=False, bbox=True)
     assert want["P"] > 1 << 20 and want["T"] <= want["P"]
     t_off = _guarded(R + 1)
-    M = gpu.region_windows_device(_to_dev(reg.reshape(-1)), 512, 300, R, t_off)
-    a = _host(t_off)
+    M = gpu.region_windows_device(to_dev(reg.reshape(-1)), 512, 300, R, t_off)
+    a = to_host(t_off)
     assert M == int(want["offsets"][-1]) and np.array_equal(a[:R + 1], want["offsets"]) and (a[R + 1:] == FILL).all()
 
 
@@ -398,7 +224,7 @@ def test_a_map_with_too_many_block_rows_is_refused_and_nothing_is_written(gpu):
     h, w = reg.shape
     model = windows_model(reg, R, None, 4, 0, lists=False)
     assert (model["P"], model["T"]) == (50, 98)
-    t_reg, t_px = _to_dev(reg.reshape(-1)), _to_dev(_frame(w, h))
+    t_reg, t_px = to_dev(reg.reshape(-1)), to_dev(frame(w, h))
     t = {k: _guarded(w * h) for k in ARRAYS}
     t["offsets"] = _guarded(R + 1)
     p = lambda v: ctypes.c_void_p(v.data_ptr())   # noqa: E731
@@ -406,7 +232,7 @@ def test_a_map_with_too_many_block_rows_is_refused_and_nothing_is_written(gpu):
                                              p(t["coords"]), p(t["index"]), p(t_px), p(t["colors"]), None)
     assert rc == -2
     for k, v in t.items():
-        assert (_host(v) == FILL).all(), k
+        assert (to_host(v) == FILL).all(), k
     with pytest.raises(gpu.RegionRowsError):
         gpu.region_windows_device(t_reg, w, h, R, t["offsets"], block=4, expand=0)
     with pytest.raises(gpu.RegionRowsError):
@@ -415,7 +241,7 @@ def test_a_map_with_too_many_block_rows_is_refused_and_nothing_is_written(gpu):
     with pytest.raises(gpu.RegionRowsError):
         gpu.quant_region_windows_device(t_reg, w, h, R, t_px, 4, t["offsets"], block=4, expand=0, capacity=w * h,
                                         t_out=t["index"], cts=cts, k_outs=k_outs)
-    assert (_host(t["index"]) == FILL).all() and (_host(t["offsets"]) == FILL).all()
+    assert (to_host(t["index"]) == FILL).all() and (to_host(t["offsets"]) == FILL).all()
     assert (cts == FILL).all() and (k_outs == FILL).all()
 
 
@@ -432,7 +258,7 @@ def test_two_streams_from_two_threads(gpu):
             name, d, e = cases[i]
             reg, R = wmap(name)
             for _ in range(3):
-                got[i] = _run(gpu, reg, R, _frame(reg.shape[1], reg.shape[0]), d, e, stream=streams[i])
+                got[i] = _run(gpu, reg, R, frame(reg.shape[1], reg.shape[0]), d, e, stream=streams[i])
         except BaseException as err:   # noqa: B036 (reported by the test's thread)
             errors.append(err)
     threads = [threading.Thread(target=work, args=(i,)) for i in range(2)]
@@ -443,7 +269,7 @@ def test_two_streams_from_two_threads(gpu):
     assert not errors, errors
     for i, (name, d, e) in enumerate(cases):
         reg, R = wmap(name)
-        _same(got[i], windows_model(reg, R, _frame(reg.shape[1], reg.shape[0]), d, e))
+        _same(got[i], windows_model(reg, R, frame(reg.shape[1], reg.shape[0]), d, e))
 
 
 # 14. The host forms.
@@ -451,7 +277,7 @@ def test_two_streams_from_two_threads(gpu):
 def test_host_form(gpu, name, kind):
     reg, R = wmap(name)
     h, w = reg.shape
-    px, mask = _frame(w, h), mask_of(kind, h, w)
+    px, mask = frame(w, h), mask_of(kind, h, w)
     area = np.bincount(reg.reshape(-1), minlength=R).astype(np.uint32)
     want = windows_model(reg, R, px, 4, 2, mask, area, 2)
     offsets, index, coords, colours = gpu.region_windows(reg, mask=mask, area=area, min_area=2, pixels=px)
@@ -476,14 +302,14 @@ def _check_pipeline(gpu, reg, R, px, k, mask, against_regions_call, host_form):
     h, w = reg.shape
     want = windows_model(reg, R, px, 4, 2, mask)
     off, M = want["offsets"].astype(np.int64), int(want["offsets"][-1])
-    t_reg, t_px = _to_dev(reg.reshape(-1)), _to_dev(px)
-    t_mask = _to_dev(mask.reshape(-1), np.uint8) if mask is not None else None
+    t_reg, t_px = to_dev(reg.reshape(-1)), to_dev(px)
+    t_mask = to_dev(mask.reshape(-1), np.uint8) if mask is not None else None
     t_off, t_out, t_colors = _guarded(R + 1), _guarded(M), _guarded(M)
     cts, k_outs = np.full((R, k), FILL, np.uint32), np.full(R, FILL, np.uint32)
     got_cts, got_k, empty = gpu.quant_region_windows_device(t_reg, w, h, R, t_px, k, t_off, t_mask=t_mask, capacity=M,
                                                             t_out=t_out, t_colors=t_colors, cts=cts, k_outs=k_outs)
     assert got_cts is cts and got_k is k_outs and empty >= 0
-    a, c, o = _host(t_out), _host(t_colors), _host(t_off)
+    a, c, o = to_host(t_out), to_host(t_colors), to_host(t_off)
     assert (a[M:] == FILL).all() and (c[M:] == FILL).all() and (o[R + 1:] == FILL).all()
     assert np.array_equal(o[:R + 1], want["offsets"]) and np.array_equal(c[:M], want["colors"])
     mapped = a[:M]
@@ -497,12 +323,12 @@ def _check_pipeline(gpu, reg, R, px, k, mask, against_regions_call, host_form):
         assert np.array_equal(mapped[off[r]:off[r + 1]], ref_out), r
     if against_regions_call:
         present = [r for r in range(R) if off[r + 1] > off[r]]
-        t_ins = [_to_dev(want["colors"][off[r]:off[r + 1]]) for r in present]
+        t_ins = [to_dev(want["colors"][off[r]:off[r + 1]]) for r in present]
         t_outs = [_guarded(int(off[r + 1] - off[r])) for r in present]
         ref_cts, _ = gpu.quant_weighted_regions_device(t_ins, t_outs, k)
         for r, ct, t in zip(present, ref_cts, t_outs):
             assert np.array_equal(cts[r, :k_outs[r]], ct), r
-            assert np.array_equal(_host(t)[:-GUARD], mapped[off[r]:off[r + 1]]), r
+            assert np.array_equal(to_host(t)[:-GUARD], mapped[off[r]:off[r + 1]]), r
     # without the mapped colours and without a capacity: the call's own colours, the same tables
     cts2, k2, empty2 = gpu.quant_region_windows_device(t_reg, w, h, R, t_px, k, _guarded(R + 1), t_mask=t_mask)
     assert empty2 == empty and np.array_equal(k2, k_outs)
@@ -513,7 +339,7 @@ def _check_pipeline(gpu, reg, R, px, k, mask, against_regions_call, host_form):
         t_short = _guarded(M)
         with pytest.raises(gpu.WindowsCapacityError):
             gpu.quant_region_windows_device(t_reg, w, h, R, t_px, k, t_off, t_mask=t_mask, capacity=M - 1, t_out=t_short)
-        assert (_host(t_short) == FILL).all()
+        assert (to_host(t_short) == FILL).all()
     if host_form:
         offsets, out, cts3, k3, empty3 = gpu.quant_region_windows(reg, px, k, num_regions=R, mask=mask)
         assert np.array_equal(offsets, want["offsets"]) and np.array_equal(out, mapped) and empty3 == empty
@@ -532,13 +358,13 @@ def test_pipeline_on_islands_with_an_empty_window(gpu):
 
 def test_pipeline_on_noise_with_a_mask(gpu):
     reg, R = wmap("noise64x48")
-    k_outs = _check_pipeline(gpu, reg, R, _frame(64, 48), 4, mask_of("random", 48, 64), True, False)
+    k_outs = _check_pipeline(gpu, reg, R, frame(64, 48), 4, mask_of("random", 48, 64), True, False)
     assert (k_outs >= 1).all() and (k_outs <= 4).all()
 
 
 def test_pipeline_with_a_window_above_the_one_launch_limit(gpu):
     reg, R = wmap("big")
-    px = _frame(512, 300) & np.uint32(0x00F0F0F0)          # (4096 colours at most)
+    px = frame(512, 300) & np.uint32(0x00F0F0F0)          # (4096 colours at most)
     want = windows_model(reg, R, px, 4, 2, lists=False)
     assert int(np.diff(want["offsets"].astype(np.int64))[0]) == 512 * 300 > 131071
     _check_pipeline(gpu, reg, R, px, 4, None, False, False)

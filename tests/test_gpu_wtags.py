@@ -1,15 +1,11 @@
 """GPU: the tag histogram of every capture window and the inside / outside
 votes of a window's quant (include/dq_hip.h, "window tags").
 
-The reference is numpy, written from the definition alone and using none of the
-code under test.  tags_model takes the window lists of test_gpu_windows.py's
-windows_model: per row reg.flat[index[lo:hi]], np.unique with the first
-indexes and the counts, ordered by first index; the best other is the largest
-count among the other ids, ties to the lowest id.  votes_model walks the list
-entries with the definition's lowest-matching-entry rule.  Equality is exact
-everywhere: array_equal on every array, == on every scalar.  Every output
-buffer is pre-filled with a sentinel and carries guard words behind its last
-entry.
+The references are tags_model and votes_model of wtags_model.py, numpy written
+from the definition alone and using none of the code under test.  Equality is
+exact everywhere: array_equal on every array, == on every scalar.  Every
+output buffer is pre-filled with a sentinel and carries guard words behind its
+last entry.
 
 Shapes are the smallest at which each mechanism can fail: the windows tests'
 maps (clipped blocks, overlapping windows, one region per pixel with up to 192
@@ -24,80 +20,23 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
-from test_gpu_merge import _frame, _noise, regions_model
-from test_gpu_windows import CASES, mask_of, windows_model, wmap
+from region_dev import body, guarded, same, to_dev, to_host
+from region_inputs import CASES, frame, mask_of, noise, tie_map, wmap
+from regions_model import regions_model
+from windows_model import windows_model
+from wtags_model import NONE, tags_model, votes_model
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 8
 FILL = 0xA5A5A5A5
-NONE = 0xFFFFFFFF
 ENTRY = ("ids", "counts", "first")
 REGION = ("inside", "best", "best_count")
+_guarded = functools.partial(guarded, guard=GUARD, fill=FILL)
 
 
-# ---------------------------------------------------------------------------
-# The references.
-def tags_model(reg2d, R, d, e, mask=None, area=None, min_area=0):
-    """The outputs of the definition, from the window lists of windows_model."""
-    reg2d = np.asarray(reg2d)
-    flat = reg2d.reshape(-1)
-    wm = windows_model(reg2d, R, np.zeros(reg2d.size, np.uint32), d, e, mask, area, min_area)
-    off, index = wm["offsets"].astype(np.int64), wm["index"].astype(np.int64)
-    rows = np.zeros(R + 1, np.int64)
-    ids, counts, first = [], [], []
-    inside, best, best_count = np.zeros(R, np.uint32), np.full(R, NONE, np.uint32), np.zeros(R, np.uint32)
-    for r in range(R):
-        tags = flat[index[off[r]:off[r + 1]]]
-        tags = np.where(tags < R, tags, NONE)
-        s, f, c = np.unique(tags, return_index=True, return_counts=True)
-        keep = s != NONE                       # (ids >= R are counted in no entry)
-        s, f, c = s[keep], f[keep], c[keep]
-        order = np.argsort(f, kind="stable")
-        s, f, c = s[order], f[order], c[order]
-        rows[r + 1] = rows[r] + len(s)
-        ids.append(s), counts.append(c), first.append(f)
-        inside[r] = c[s == r].sum()
-        other = s != r
-        if other.any():
-            top = c[other].max()
-            best[r], best_count[r] = s[other][c[other] == top].min(), top
-    cat = lambda parts: (np.concatenate(parts) if parts else np.zeros(0)).astype(np.uint32)   # noqa: E731
-    out = dict(rows=rows.astype(np.uint32), ids=cat(ids), counts=cat(counts), first=cat(first), inside=inside,
-               best=best, best_count=best_count, offsets=wm["offsets"], E=int(rows[-1]))
-    for v in out.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return out
-
-
-def votes_model(flat, R, offsets, index, mapped, cts, k_outs, k):
-    """(votes (R, 2, k), best (R, 2), misses) of the definition."""
-    off = np.asarray(offsets, np.int64)
-    owner = np.repeat(np.arange(R, dtype=np.int64), np.diff(off))
-    idx = np.asarray(index, np.int64)[:len(owner)]
-    side = (np.asarray(flat, np.int64)[idx] != owner).astype(np.int64)
-    colour = np.asarray(mapped, np.uint32)[:len(owner)] & np.uint32(0xFFFFFF)
-    cts = np.asarray(cts, np.uint32).reshape(R, k)
-    hit = np.full(len(owner), k, np.int64)
-    for i in range(k - 1, -1, -1):             # (downwards: the lowest matching entry stays)
-        match = ((cts[owner, i] & np.uint32(0xFFFFFF)) == colour) & (i < np.asarray(k_outs, np.int64)[owner])
-        hit[match] = i
-    found = hit < k
-    votes = np.bincount((owner[found] * 2 + side[found]) * k + hit[found], minlength=R * 2 * k).astype(np.uint32)
-    votes = votes.reshape(R, 2, k)
-    best = np.where(votes.max(axis=2) > 0, votes.argmax(axis=2), NONE).astype(np.uint32)   # (argmax: the lowest)
-    return votes, best, int((~found).sum())
-
-
-@functools.lru_cache(maxsize=None)
-def tie_map(order):
-    """4 rows x 12 columns, three 4 x 4 blocks with the ids `order`: at d = 4, e = 1 row 0 of [1, 0, 2]
-    (and of [2, 0, 1]) holds all three ids with 16 pixels each."""
-    reg = np.repeat(np.array(order, np.uint32), 4)[None, :].repeat(4, axis=0)
-    reg = np.ascontiguousarray(reg)
-    reg.setflags(write=False)
-    return reg, 3
+def _take(t, size, what):
+    return body(t, size, GUARD, FILL, what)
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,35 +54,14 @@ def _model(name, d, e, kind=None, min_area=None):
 
 
 # ---------------------------------------------------------------------------
-def _to_dev(a, dtype=np.uint32):
-    import torch
-    a = np.ascontiguousarray(a, dtype)
-    return torch.from_numpy(a.view(np.int32 if dtype == np.uint32 else np.uint8).copy()).to("cuda:0")
-
-
-def _guarded(count):
-    import torch
-    return torch.full((count + GUARD,), FILL - (1 << 32), dtype=torch.int32, device="cuda:0")
-
-
-def _host(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _take(t, size, what):
-    a = _host(t)
-    assert (a[size:] == FILL).all(), "guard words of %s" % what
-    return a[:size]
-
-
 def _run(gpu, reg, R, d, e, mask=None, area=None, min_area=0, stream=None, cap=None):
     """window_tags_device on fresh guarded tensors: the count-only call, then the call with `cap`
     (default: E) -> dict of every array and E; the entry arrays are None when they were left alone."""
     import torch
     h, w = reg.shape
-    t_reg = _to_dev(reg.reshape(-1))
-    t_mask = _to_dev(mask.reshape(-1), np.uint8) if mask is not None else None
-    t_area = _to_dev(area) if area is not None else None
+    t_reg = to_dev(reg.reshape(-1))
+    t_mask = to_dev(mask.reshape(-1), np.uint8) if mask is not None else None
+    t_area = to_dev(area) if area is not None else None
     t_rows = _guarded(R + 1)
     if stream is not None:   # (the tensors above were filled on the current stream, the sentinel included: a
         stream.wait_stream(torch.cuda.current_stream())   # fill that ran after the call would undo its output)
@@ -167,19 +85,17 @@ def _run(gpu, reg, R, d, e, mask=None, area=None, min_area=0, stream=None, cap=N
         out[k] = _take(t[k], R, k)
     for k in ENTRY:
         if E <= cap:
-            out[k] = _take(t[k], E, k)
-            assert (_host(t[k])[E:] == FILL).all(), k
+            out[k] = _take(t[k], max(cap, E), k)[:E]
+            assert (to_host(t[k])[E:] == FILL).all(), k
         else:
-            assert (_host(t[k]) == FILL).all(), k
+            assert (to_host(t[k]) == FILL).all(), k
             out[k] = None
     return out
 
 
 def _same(got, want, keys=("rows", "offsets") + ENTRY + REGION):
     assert got["E"] == want["E"]
-    for k in keys:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
-        assert np.array_equal(got[k], want[k]), k
+    same(got, want, keys)
 
 
 def _check(gpu, name, d, e, kind=None, min_area=None):
@@ -255,7 +171,7 @@ def test_ties_go_to_the_lowest_id(gpu, order):
 def test_a_refused_map_writes_nothing(gpu):
     reg, R = wmap("refused")
     h, w = reg.shape
-    t_reg = _to_dev(reg.reshape(-1))
+    t_reg = to_dev(reg.reshape(-1))
     t = {k: _guarded(R + 1) for k in ("rows", "offsets")}
     t.update({k: _guarded(64) for k in ENTRY})
     t.update({k: _guarded(R) for k in REGION})
@@ -265,12 +181,12 @@ def test_a_refused_map_writes_nothing(gpu):
                                           p(t["best_count"]), p(t["offsets"]), None)
     assert rc == -2
     for k, v in t.items():
-        assert (_host(v) == FILL).all(), k
+        assert (to_host(v) == FILL).all(), k
     with pytest.raises(gpu.RegionRowsError):
         gpu.window_tags_device(t_reg, w, h, R, t["rows"], block=4, expand=0)
     with pytest.raises(gpu.RegionRowsError):
         gpu.window_tags(reg, block=4, expand=0)
-    assert (_host(t["rows"]) == FILL).all()
+    assert (to_host(t["rows"]) == FILL).all()
 
 
 # 7. cap: E alone; one short leaves the entries alone and writes the rest; E writes them.
@@ -283,7 +199,7 @@ def test_capacity(gpu):
     _same(_run(gpu, reg, R, 4, 2, cap=want["E"]), want)
     _same(_run(gpu, reg, R, 4, 2, cap=want["E"] + 5), want)
     t_rows, t_ids = _guarded(R + 1), _guarded(want["E"])
-    assert gpu.window_tags_device(_to_dev(reg.reshape(-1)), 97, 41, R, t_rows, capacity=want["E"], t_ids=t_ids) \
+    assert gpu.window_tags_device(to_dev(reg.reshape(-1)), 97, 41, R, t_rows, capacity=want["E"], t_ids=t_ids) \
         == want["E"]                                       # one entry array alone, no per-region array
     assert np.array_equal(_take(t_ids, want["E"], "ids"), want["ids"])
 
@@ -300,14 +216,14 @@ def test_block_one_expand_zero_rows_are_the_areas(gpu):
 
 
 def test_block_one_expand_one_rows_are_the_adjacency_graph(gpu):
-    lab = _noise(97, 41, 3)
-    reg, _ = regions_model(lab, 4, _frame(97, 41))
+    lab = noise(97, 41, 3, seed=1)
+    reg, _ = regions_model(lab, 4, frame(97, 41))
     reg = np.ascontiguousarray(reg.reshape(41, 97), np.uint32)
     R = int(reg.max()) + 1
     got = _run(gpu, reg, R, 1, 1)
     owner = np.repeat(np.arange(R), np.diff(got["rows"].astype(np.int64)))
     mine = {(int(r), int(s)) for r, s in zip(owner, got["ids"]) if r != s}
-    t_reg = _to_dev(reg.reshape(-1))
+    t_reg = to_dev(reg.reshape(-1))
     E, graph = gpu.region_adjacency_device(t_reg, 97, 41, connectivity=4, edge_capacity=len(mine))
     assert 0 < E <= len(mine)
     edges = graph["edges"].cpu().numpy().view(np.uint32)
@@ -388,8 +304,8 @@ def _votes(gpu, flat, R, offsets, index, mapped, cts, k_outs, k):
     """window_votes_device on guarded tensors, against the model; returns (votes, best, misses)."""
     total = int(offsets[-1])
     t_votes, t_best = _guarded(R * 2 * k), _guarded(R * 2)
-    misses = gpu.window_votes_device(_to_dev(flat), len(flat), R, _to_dev(offsets), _to_dev(index), total,
-                                     _to_dev(mapped), np.ascontiguousarray(cts, np.uint32),
+    misses = gpu.window_votes_device(to_dev(flat), len(flat), R, to_dev(offsets), to_dev(index), total,
+                                     to_dev(mapped), np.ascontiguousarray(cts, np.uint32),
                                      np.ascontiguousarray(k_outs, np.uint32), k, t_votes, t_best)
     votes, best = _take(t_votes, R * 2 * k, "votes").reshape(R, 2, k), _take(t_best, R * 2, "best").reshape(R, 2)
     want_votes, want_best, want_misses = votes_model(flat, R, offsets, index, mapped, cts, k_outs, k)
@@ -487,8 +403,8 @@ def test_pipeline_on_islands(gpu):
     px = np.where(reg.reshape(-1) == 0, 0x202020 + noise, 0xC0C0C0 + noise).astype(np.uint32)   # islands bright
     wm = windows_model(reg, R, px, 4, 2)
     M = int(wm["offsets"][-1])
-    t_reg, t_off, t_index, t_out = _to_dev(reg.reshape(-1)), _guarded(R + 1), _guarded(M), _guarded(M)
-    cts, k_outs, _ = gpu.quant_region_windows_device(t_reg, w, h, R, _to_dev(px), k, t_off, capacity=M, t_out=t_out,
+    t_reg, t_off, t_index, t_out = to_dev(reg.reshape(-1)), _guarded(R + 1), _guarded(M), _guarded(M)
+    cts, k_outs, _ = gpu.quant_region_windows_device(t_reg, w, h, R, to_dev(px), k, t_off, capacity=M, t_out=t_out,
                                                      t_index=t_index)
     assert np.array_equal(_take(t_index, M, "index"), wm["index"])
     t_votes, t_best = _guarded(R * 2 * k), _guarded(R * 2)

@@ -1,7 +1,7 @@
 """The inputs of test_gpu_regions_atsize.py and the thresholds they are there to
 cross (no GPU).
 
-Two label maps of 1100 x 1000 pixels, 4-connected, from test_gpu_regions._noise:
+Two label maps of 1100 x 1000 pixels, 4-connected, from region_inputs.noise:
 A (three labels) and B (200 labels), and the area arrays of the size order
 alone.  The builders below run the stage suites' own models on them, once per
 session (lru_cache); the GPU file imports them from here.  The tests assert
@@ -14,9 +14,10 @@ import functools
 import numpy as np
 
 import containment_model as cm
-from test_gpu_adjacency import adjacency_model
-from test_gpu_pixels import rows_total
-from test_gpu_regions import _frame, _noise, flood_fill_regions
+import region_inputs
+from adjacency_model import adjacency_model
+from pixels_model import rows_total
+from regions_model import flood_fill_regions
 
 W, H = 1100, 1000
 N = W * H
@@ -33,13 +34,13 @@ def _frozen(arrays):
 
 @functools.lru_cache(maxsize=None)
 def labels(name):
-    lab = _noise(W, H, LABELS[name])
+    lab = region_inputs.noise(W, H, LABELS[name], dtype=np.int64)
     lab.setflags(write=False)
     return lab
 
 
 def frame():
-    return _frame(W, H)
+    return region_inputs.frame(W, H)
 
 
 @functools.lru_cache(maxsize=None)
@@ -76,7 +77,7 @@ def test_the_maps_have_more_than_1024_chunks():
     # top scan covers 1024 * 1024 pixels
     assert N > 1048576
     for name in LABELS:
-        assert labels(name).shape == (H, W) and int(labels(name).max()) < 256   # (_widen takes them)
+        assert labels(name).shape == (H, W) and int(labels(name).max()) < 256   # (widen takes them)
 
 
 def test_map_b_crosses_the_shared_scan_and_the_stride_loops():

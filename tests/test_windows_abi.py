@@ -14,12 +14,9 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
-from test_gpu_merge import _frame
-from test_gpu_pixels import lists_model
-from test_gpu_windows import CASES, dilate_square, window_grids, windows_model, wmap
-
-FAKE = {name: 0x10000 * (i + 1) for i, name in enumerate(
-    ["regions", "offsets", "coords", "index", "pixels", "colors", "mask", "area", "out", "cts", "k_outs"])}
+from pixels_model import lists_model
+from region_inputs import CASES, WINDOWS_FAKE as FAKE, WINDOWS_SHAPES as SHAPES, frame, wmap
+from windows_model import dilate_square, window_grids, windows_model
 
 GOOD = dict(regions=FAKE["regions"], width=16, height=8, nregions=5, block=4, expand=2, mask=FAKE["mask"] + 1,
             area=FAKE["area"], min_area=3, offsets=FAKE["offsets"], cap=1000, coords=FAKE["coords"],
@@ -52,33 +49,6 @@ def _quant(lib, host, **kw):
     args = _window_args(a) + (a["k"], _p(a["out"]), _p(a["cts"]), _p(a["k_outs"]), a["max_iters"])
     return lib.dq_hip_quant_region_windows(*args) if host else lib.dq_hip_quant_region_windows_dev(0, *args, None)
 
-
-SHAPES = {
-    "null_regions": dict(regions=None),
-    "null_offsets": dict(offsets=None),
-    "width_0": dict(width=0),
-    "height_0": dict(height=0),
-    "width_65536": dict(width=65536, height=1),
-    "height_65536": dict(width=1, height=65536),
-    "pixels_2^31": dict(width=65535, height=32769),      # 2^31 + 32767
-    "pixels_65535x65535": dict(width=65535, height=65535),
-    "nregions_0": dict(nregions=0),
-    "nregions_2^31": dict(nregions=1 << 31),
-    "nregions_max_u32": dict(nregions=0xFFFFFFFF),
-    "block_0": dict(block=0),
-    "block_9": dict(block=9),
-    "block_max_u32": dict(block=0xFFFFFFFF),
-    "expand_4": dict(expand=4),
-    "expand_max_u32": dict(expand=0xFFFFFFFF),
-    "regions_2mod4": dict(regions=FAKE["regions"] + 2),
-    "regions_odd": dict(regions=FAKE["regions"] + 1),
-    "offsets_2mod4": dict(offsets=FAKE["offsets"] + 2),
-    "area_2mod4": dict(area=FAKE["area"] + 2),
-    "coords_odd": dict(coords=FAKE["coords"] + 1),
-    "index_2mod4": dict(index=FAKE["index"] + 2),
-    "colors_2mod4": dict(colors=FAKE["colors"] + 2),
-    "pixels_2mod4": dict(pixels=FAKE["pixels"] + 2),
-}
 
 BAD = dict(SHAPES, **{
     "colors_without_pixels": dict(pixels=None),
@@ -137,7 +107,7 @@ def test_the_header_declares_the_entries_and_the_abi_version_stays(pkg):
 @pytest.mark.parametrize("name", ["rows65", "comb"])
 def test_the_model_at_block_one_expand_zero_is_the_pixel_lists_model(name):
     reg, R = wmap(name)
-    px = _frame(reg.shape[1], reg.shape[0])
+    px = frame(reg.shape[1], reg.shape[0])
     got, want = windows_model(reg, R, px, 1, 0), lists_model(reg, R, px)
     for k in ("offsets", "index", "coords", "colors"):
         assert np.array_equal(got[k], want[k]), k
@@ -155,7 +125,7 @@ def test_every_map_of_the_gpu_tests_is_one_the_call_takes():
 
 def test_the_model_cut_to_bounding_boxes_is_the_model():
     reg, R = wmap("noise64x48")
-    px = _frame(64, 48)
+    px = frame(64, 48)
     whole, cut = windows_model(reg, R, px, 4, 2), windows_model(reg, R, px, 4, 2, bbox=True)
     for k in ("offsets", "index", "P", "T"):
         assert np.array_equal(whole[k], cut[k]), k

@@ -14,9 +14,9 @@ import numpy as np
 import pytest
 
 import dq_fixtures as fx
-from test_gpu_windows import CASES, windows_model, wmap
-from test_gpu_wtags import NONE, tags_model, tie_map, votes_model
-from test_windows_abi import SHAPES
+from region_inputs import CASES, WINDOWS_SHAPES as SHAPES, tie_map, wmap
+from windows_model import windows_model
+from wtags_model import NONE, tags_model, votes_model
 
 FAKE = {name: 0x10000 * (i + 1) for i, name in enumerate(
     ["regions", "offsets", "rows", "ids", "counts", "first", "inside", "best", "best_count", "mask", "area", "index",

@@ -24,7 +24,7 @@ device work, the read-back of the head count between its two halves included):
     adjacency_count_ms  the count-only call (capacity 0, no array)
     copy_pass_ms        a plain device pass that moves what one pass over the map
                         must move at least: n label bytes read, 4 n written
-    host_ms             the numpy model of tests/test_gpu_adjacency.py on one
+    host_ms             the numpy model of tests/adjacency_model.py on one
                         core, once, and whether it agrees on E
 heads / table_slots / scratch_bytes: the heads are recomputed here on the host
 by the rule of csrc/dq_adjacency.hip (per direction, runs of equal id pairs
@@ -35,20 +35,14 @@ the adjacency_*_kernel rows.  DQ_HIP_LIB selects another build of the library
 (the insert pass without LDS slots).  Prints one JSON object (and writes it to --out).
 """
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import ab_common as ab
 
-W4K, H4K = 3840, 2160
 NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
@@ -87,39 +81,18 @@ def main():
     a = ap.parse_args()
 
     import torch
-    import dq_fixtures as fx
     from __graft_entry__ import load_package
-    from regions_ab import smooth_frame
     pkg = load_package()
 
-    if a.input == "smooth":
-        px, w, h, k = smooth_frame(W4K, H4K), W4K, H4K, 256
-    elif a.input == "noise":
-        px, w, h, k = pkg.synth_frame(W4K * H4K), W4K, H4K, 256
-    else:
-        px, w, h = fx.load_png_u32(os.path.join(ROOT, "tests", "golden", "png", "batman.png"))
-        k = 16
+    px, w, h, k = ab.load_input(pkg, a.input)
     n = w * h
     stream = torch.cuda.Stream(device="cuda:0")
 
     def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        ms = []
-        for _ in range(a.steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return statistics.median(ms)
+        return statistics.median(ab.timed(stream, fn, a.steps, a.warmup))
 
     t_px = torch.from_numpy(px.view(np.int32)).to("cuda:0")
-    t_lab = torch.empty(n, dtype=torch.uint8, device="cuda:0")
-    cts, _ = pkg.quant_labels_batch_device([t_px], [t_lab], k)
-    t_reg = torch.empty(n, dtype=torch.int32, device="cuda:0")
-    R, _ = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=a.connectivity)
+    cts, t_lab, t_reg, R = ab.region_map(pkg, t_px, w, h, k, a.connectivity)
     torch.cuda.synchronize()
 
     adj = lambda **kw: pkg.region_adjacency_device(t_reg, w, h, connectivity=a.connectivity,  # noqa: E731
@@ -148,11 +121,11 @@ def main():
     row["scratch_bytes"] = slots * 24 + 4 * ((n + 1023) // 1024) + 4
     row["scratch_bytes_count_only"] = slots * 16 + 4 * ((n + 1023) // 1024) + 4
     if not a.no_host:
-        from test_gpu_adjacency import adjacency_model
+        from adjacency_model import adjacency_model
         t0 = time.perf_counter()
         m = adjacency_model(reg2d, a.connectivity, px, R)
         row["host_ms"] = (time.perf_counter() - t0) * 1e3
-        row["host_how"] = "numpy model (tests/test_gpu_adjacency.py), one core"
+        row["host_how"] = "numpy model (tests/adjacency_model.py), one core"
         row["host_edges"] = int(m["E"])
         row["host_agrees"] = bool(
             m["E"] == E and np.array_equal(m["edges"], g["edges"].cpu().numpy().view(np.uint32))
@@ -161,12 +134,7 @@ def main():
             and np.array_equal(m["step"], g["step"].cpu().numpy().view(np.uint64))
             and np.array_equal(m["degree"], g["degree"].cpu().numpy().view(np.uint32)))
 
-    line = json.dumps(row, sort_keys=True)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ab.emit(row, a.out)
 
 
 if __name__ == "__main__":

@@ -41,20 +41,14 @@ gathers of per-region words left out.  Prints one JSON object (and writes it
 to --out).
 """
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import ab_common as ab
 
-W4K, H4K = 3840, 2160
 BYTES_PER_PIXEL = 4.25 + 2.25 + 18 + 6 + 6 + 4
 
 
@@ -84,43 +78,20 @@ def main():
     a = ap.parse_args()
 
     import torch
-    import dq_fixtures as fx
     from __graft_entry__ import load_package
-    from regions_ab import smooth_frame
     pkg = load_package()
 
-    if a.input == "smooth":
-        px, w, h, k = smooth_frame(W4K, H4K), W4K, H4K, 256
-    elif a.input == "noise":
-        px, w, h, k = pkg.synth_frame(W4K * H4K), W4K, H4K, 256
-    else:
-        px, w, h = fx.load_png_u32(os.path.join(ROOT, "tests", "golden", "png", "batman.png"))
-        k = 16
+    px, w, h, k = ab.load_input(pkg, a.input)
     n, conn = w * h, a.connectivity
     stream = torch.cuda.Stream(device="cuda:0")
 
     def timed(fn, steps):
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return ms
+        return ab.timed(stream, fn, steps)
 
     t_px = torch.from_numpy(px.view(np.int32)).to("cuda:0")
-    t_lab = torch.empty(n, dtype=torch.uint8, device="cuda:0")
-    pkg.quant_labels_batch_device([t_px], [t_lab], k)
-    t_reg = torch.empty(n, dtype=torch.int32, device="cuda:0")
-    R, _ = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=conn)
+    _, t_lab, t_reg, R = ab.region_map(pkg, t_px, w, h, k, conn)
     if a.input == "segments":
-        R, st = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=conn, stats_capacity=R, t_pixels=t_px)
-        E, _ = pkg.region_adjacency_device(t_reg, w, h, connectivity=conn)
-        E, g = pkg.region_adjacency_device(t_reg, w, h, connectivity=conn, edge_capacity=E)
-        R, _, _ = pkg.merge_regions_device(t_reg, R, st["area"], st["first"], st["sums"], g["edges"], 10,
-                                           num_edges=E, stats_capacity=R)
+        R, _ = ab.segments_in_place(pkg, t_reg, *ab.region_graph(pkg, t_px, t_lab, t_reg, w, h, R, conn))
     torch.cuda.synchronize()
 
     def distance():
@@ -175,12 +146,7 @@ def main():
         row["host_agrees"] = bool(np.array_equal(d[on], dev[on]))
         del up
 
-    line = json.dumps(row, sort_keys=True)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ab.emit(row, a.out)
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@ device work, the per-round read-backs of the link count included):
                         dq_hip_segment_labels pays for learning R and E first
     copy_pass_ms        a plain device pass that moves what one pass over the map
                         must move at least: n label bytes read, 4 n written
-    host_ms             the numpy model of tests/test_gpu_merge.py on one core,
+    host_ms             the numpy model of tests/merge_model.py on one core,
                         once, and whether every array it gives equals the device's
 launches_derived / readbacks_derived / scratch_bytes_derived are NOT observed:
 they follow from the rounds, R and n by the formulas of csrc/dq_merge.h and
@@ -42,20 +42,13 @@ the merge_*_kernel rows.  DQ_HIP_LIB selects another build of the library (the
 fold pass without LDS slots).  Prints one JSON object (and writes it to --out).
 """
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-W4K, H4K = 3840, 2160
+import ab_common as ab
 
 
 def main():
@@ -70,42 +63,19 @@ def main():
     a = ap.parse_args()
 
     import torch
-    import dq_fixtures as fx
     from __graft_entry__ import load_package
-    from regions_ab import smooth_frame
     pkg = load_package()
 
-    if a.input == "smooth":
-        px, w, h, k = smooth_frame(W4K, H4K), W4K, H4K, 256
-    elif a.input == "noise":
-        px, w, h, k = pkg.synth_frame(W4K * H4K), W4K, H4K, 256
-    else:
-        px, w, h = fx.load_png_u32(os.path.join(ROOT, "tests", "golden", "png", "batman.png"))
-        k = 16
+    px, w, h, k = ab.load_input(pkg, a.input)
     n = w * h
     stream = torch.cuda.Stream(device="cuda:0")
 
     def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        ms = []
-        for _ in range(a.steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return statistics.median(ms)
+        return statistics.median(ab.timed(stream, fn, a.steps, a.warmup))
 
     t_px = torch.from_numpy(px.view(np.int32)).to("cuda:0")
-    t_lab = torch.empty(n, dtype=torch.uint8, device="cuda:0")
-    cts, _ = pkg.quant_labels_batch_device([t_px], [t_lab], k)
-    t_reg = torch.empty(n, dtype=torch.int32, device="cuda:0")
-    R, _ = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=a.connectivity)
-    R, st = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=a.connectivity, stats_capacity=R, t_pixels=t_px)
-    E, _ = pkg.region_adjacency_device(t_reg, w, h, connectivity=a.connectivity)
-    E, g = pkg.region_adjacency_device(t_reg, w, h, connectivity=a.connectivity, edge_capacity=E)
+    cts, t_lab, t_reg, R = ab.region_map(pkg, t_px, w, h, k, a.connectivity)
+    R, st, E, g = ab.region_graph(pkg, t_px, t_lab, t_reg, w, h, R, a.connectivity)
     t_edges = g["edges"] if E else None
     t_out = torch.empty(n, dtype=torch.int32, device="cuda:0")
     torch.cuda.synchronize()
@@ -142,7 +112,7 @@ def main():
     row["copy_pass_bytes"] = 5 * n
 
     if not a.no_host:
-        from test_gpu_merge import merge_model
+        from merge_model import merge_model
         u = lambda t, d=np.uint32: t.cpu().numpy().view(d)  # noqa: E731
         host = {key: u(st[key], np.uint64 if key == "sums" else np.uint32) for key in ("area", "first", "sums", "bbox")}
         edges = u(t_edges).reshape(-1, 2) if E else np.zeros((0, 2), np.uint32)
@@ -150,7 +120,7 @@ def main():
         t0 = time.perf_counter()
         m = merge_model(reg, host["area"], host["first"], host["sums"], host["bbox"], edges, a.min_area)
         row["host_ms"] = (time.perf_counter() - t0) * 1e3
-        row["host_how"] = "numpy model (tests/test_gpu_merge.py), one core"
+        row["host_how"] = "numpy model (tests/merge_model.py), one core"
         row["host_segments"], row["host_rounds"] = int(m["R"]), int(m["rounds"])
         row["host_agrees"] = bool(
             m["R"] == R2 and m["rounds"] == rounds and np.array_equal(m["regions"], u(out["regions"]))
@@ -158,12 +128,7 @@ def main():
             and np.array_equal(m["first"], u(out["first"])) and np.array_equal(m["bbox"], u(out["bbox"]))
             and np.array_equal(m["sums"], u(out["sums"], np.uint64)))
 
-    line = json.dumps(row, sort_keys=True)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ab.emit(row, a.out)
 
 
 if __name__ == "__main__":

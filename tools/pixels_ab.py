@@ -41,20 +41,13 @@ run of its own (rocprofv3 --kernel-trace --stats -- python tools/pixels_ab.py
 Prints one JSON object (and writes it to --out).
 """
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-W4K, H4K = 3840, 2160
+import ab_common as ab
 
 
 def main():
@@ -71,42 +64,21 @@ def main():
     a = ap.parse_args()
 
     import torch
-    import dq_fixtures as fx
     from __graft_entry__ import load_package
-    from regions_ab import smooth_frame
     pkg = load_package()
 
-    if a.input == "smooth":
-        px, w, h, k = smooth_frame(W4K, H4K), W4K, H4K, 256
-    elif a.input == "noise":
-        px, w, h, k = pkg.synth_frame(W4K * H4K), W4K, H4K, 256
-    else:
-        px, w, h = fx.load_png_u32(os.path.join(ROOT, "tests", "golden", "png", "batman.png"))
-        k = 16
+    px, w, h, k = ab.load_input(pkg, a.input)
     n = w * h
     dev = "cuda:0"
     stream = torch.cuda.Stream(device=dev)
 
-    def timed(fn, steps=None):
-        for _ in range(a.warmup):
-            fn()
-        ms = []
-        for _ in range(steps or a.steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return statistics.median(ms)
+    def timed(fn):
+        return statistics.median(ab.timed(stream, fn, a.steps, a.warmup))
 
     words = lambda count: torch.empty(count, dtype=torch.int32, device=dev)  # noqa: E731
     u = lambda t, d=np.uint32: t.cpu().numpy().view(d)  # noqa: E731
     t_px = torch.from_numpy(px.view(np.int32)).to(dev)
-    t_lab = torch.empty(n, dtype=torch.uint8, device=dev)
-    cts, _ = pkg.quant_labels_batch_device([t_px], [t_lab], k)
-    t_reg = words(n)
-    R, _ = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=a.connectivity)
+    cts, t_lab, t_reg, R = ab.region_map(pkg, t_px, w, h, k, a.connectivity)
     t_off, t_idx, t_crd, t_col = words(R + 1), words(n), words(n), words(n)
     torch.cuda.synchronize()
 
@@ -177,10 +149,7 @@ def main():
         del up
 
     if a.input == "batman":
-        R, st = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=a.connectivity, stats_capacity=R,
-                                         t_pixels=t_px)
-        E, _ = pkg.region_adjacency_device(t_reg, w, h, connectivity=a.connectivity)
-        E, g = pkg.region_adjacency_device(t_reg, w, h, connectivity=a.connectivity, edge_capacity=E)
+        R, st, E, g = ab.region_graph(pkg, t_px, t_lab, t_reg, w, h, R, a.connectivity)
         t_seg = words(n)
         S, _, _ = pkg.merge_regions_device(t_reg, R, st["area"], st["first"], st["sums"], g["edges"] if E else None,
                                            a.min_area, t_bbox=st["bbox"], num_edges=E, t_out_regions=t_seg,
@@ -218,12 +187,7 @@ def main():
             all(np.array_equal(cts4[r, :kouts[r]], wr.colortable(r)) for r in range(S))
             and np.array_equal(painted, u(t_out)))
 
-    line = json.dumps(row, sort_keys=True)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ab.emit(row, a.out)
 
 
 if __name__ == "__main__":

@@ -18,36 +18,19 @@ exactly its device work):
     map_ms            the label map kernel that produced the input (the library's
                       stat kind 7 of the quantise call)
     host_ms           the same regions on the host, once: scipy.ndimage.label per
-                      label value where scipy can be imported, else the test
-                      file's flood fill (only up to --host-max pixels)
+                      label value where scipy can be imported, else the flood
+                      fill of tests/regions_model.py (only up to --host-max pixels)
 The per-pass split comes from a kernel trace of this tool
 (rocprofv3 --kernel-trace --stats -- python tools/regions_ab.py --steps 10 --no-host):
 the six region_*_kernel rows.  Prints one JSON object (and writes it to --out).
 """
 import argparse
-import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-W4K, H4K = 3840, 2160
-
-
-def smooth_frame(w, h):
-    """Slow gradients in all three channels with a few broad waves."""
-    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
-    r = 127.5 + 127.5 * np.sin(xs / w * 3.0 + ys / h * 1.5)
-    g = 255.0 * ys / (h - 1)
-    b = 127.5 + 127.5 * np.cos((xs / w) ** 2 * 4.0 - ys / h * 2.0)
-    u = lambda a: np.clip(a, 0, 255).astype(np.uint32)  # noqa: E731
-    return ((u(r) << 16) | (u(g) << 8) | u(b)).reshape(-1)
+import ab_common as ab
 
 
 def host_regions(lab2d, connectivity, host_max):
@@ -65,9 +48,9 @@ def host_regions(lab2d, connectivity, host_max):
         return (time.perf_counter() - t0) * 1e3, int(count), "scipy.ndimage.label per label value"
     if lab2d.size > host_max:
         return None, None, "skipped: flood fill of %d pixels" % lab2d.size
-    from test_gpu_regions import flood_fill_regions
+    from regions_model import flood_fill_regions
     _, st = flood_fill_regions(lab2d, connectivity)
-    return (time.perf_counter() - t0) * 1e3, int(len(st["area"])), "python flood fill (tests/test_gpu_regions.py)"
+    return (time.perf_counter() - t0) * 1e3, int(len(st["area"])), "python flood fill (tests/regions_model.py)"
 
 
 def main():
@@ -81,29 +64,15 @@ def main():
     a = ap.parse_args()
 
     import torch
-    import dq_fixtures as fx
     from __graft_entry__ import load_package
     pkg = load_package()
     pkg.set_timing(True)
 
-    bat, bw, bh = fx.load_png_u32(os.path.join(ROOT, "tests", "golden", "png", "batman.png"))
-    inputs = [("smooth", smooth_frame(W4K, H4K), W4K, H4K, 256),
-              ("noise", pkg.synth_frame(W4K * H4K), W4K, H4K, 256),
-              ("batman", bat, bw, bh, 16)]
+    inputs = [(name,) + ab.load_input(pkg, name) for name in ("smooth", "noise", "batman")]
     stream = torch.cuda.Stream(device="cuda:0")
 
     def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        ms = []
-        for _ in range(a.steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return statistics.median(ms)
+        return statistics.median(ab.timed(stream, fn, a.steps, a.warmup))
 
     res = {"steps": a.steps, "connectivity": a.connectivity, "label_bytes": 1, "inputs": {}}
     for name, px, w, h, k in inputs:
@@ -140,12 +109,7 @@ def main():
         res["inputs"][name] = row
         del t_px, t_lab, t_reg
 
-    line = json.dumps(res, sort_keys=True)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ab.emit(res, a.out)
 
 
 if __name__ == "__main__":

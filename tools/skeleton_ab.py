@@ -37,20 +37,14 @@ launches and read_backs: what csrc/dq_abi_regions.cpp enqueues for the iteration
 Prints one JSON object (and writes it to --out).
 """
 import argparse
-import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import ab_common as ab
 
-W4K, H4K = 3840, 2160
 ITERS_PER_LAUNCH = 16
 
 
@@ -112,48 +106,24 @@ def main():
     a = ap.parse_args()
 
     import torch
-    import dq_fixtures as fx
     import skeleton_model as sm
     from __graft_entry__ import load_package
-    from regions_ab import smooth_frame
     pkg = load_package()
     conn = 8
     stream = torch.cuda.Stream(device="cuda:0")
 
     def timed(fn, steps):
-        ms = []
-        for _ in range(steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return ms
+        return ab.timed(stream, fn, steps)
 
     if a.input == "full":
-        w, h, R = W4K, H4K, 1
+        w, h, R = ab.W4K, ab.H4K, 1
         t_reg = torch.zeros(w * h, dtype=torch.int32, device="cuda:0")
     else:
-        if a.input == "smooth":
-            px, w, h, k = smooth_frame(W4K, H4K), W4K, H4K, 256
-        elif a.input == "noise":
-            px, w, h, k = pkg.synth_frame(W4K * H4K), W4K, H4K, 256
-        else:
-            px, w, h = fx.load_png_u32(os.path.join(ROOT, "tests", "golden", "png", "batman.png"))
-            k = 16
-        n = w * h
+        px, w, h, k = ab.load_input(pkg, a.input)
         t_px = torch.from_numpy(px.view(np.int32)).to("cuda:0")
-        t_lab = torch.empty(n, dtype=torch.uint8, device="cuda:0")
-        pkg.quant_labels_batch_device([t_px], [t_lab], k)
-        t_reg = torch.empty(n, dtype=torch.int32, device="cuda:0")
-        R, _ = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=conn)
+        _, t_lab, t_reg, R = ab.region_map(pkg, t_px, w, h, k, conn)
         if a.input == "segments":
-            R, st = pkg.label_regions_device(t_lab, w, h, t_reg, connectivity=conn, stats_capacity=R, t_pixels=t_px)
-            E, _ = pkg.region_adjacency_device(t_reg, w, h, connectivity=conn)
-            E, g = pkg.region_adjacency_device(t_reg, w, h, connectivity=conn, edge_capacity=E)
-            R, _, _ = pkg.merge_regions_device(t_reg, R, st["area"], st["first"], st["sums"], g["edges"], 10,
-                                               num_edges=E, stats_capacity=R)
+            R, _ = ab.segments_in_place(pkg, t_reg, *ab.region_graph(pkg, t_px, t_lab, t_reg, w, h, R, conn))
     torch.cuda.synchronize()
 
     def skeleton():
@@ -205,12 +175,7 @@ def main():
             row["host_agrees"] = bool(np.array_equal(model["skel"], skel) and np.array_equal(model["when"], when))
         del up
 
-    line = json.dumps(row, sort_keys=True)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ab.emit(row, a.out)
 
 
 if __name__ == "__main__":
