@@ -42,6 +42,10 @@ Skeletons of all regions of a region map (Guo-Hall thinning, the reference's
 skelReduce on every region's mask at once) with the iteration that deleted
 each pixel, the skeleton's area and the region's thickness:
     region_skeleton_device, region_skeleton
+Contours of all regions of a region map (border following, the reference's
+findContourOutline on every region's mask at once): per region the ordered
+border pixels with their chain codes, and per pixel how often it is visited:
+    region_contours_device, region_contours
 Row-tile sharding (one frame over shards / GPUs, RCCL allreduce per pass):
     quant_rows_device, comm_init_torch (comm_unique_id, comm_init, comm_destroy);
     loopback_rows_device (tests: N ranks in one process, loopback collective)
@@ -160,6 +164,10 @@ def lib():
         "dq_hip_region_skeleton_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp,
                                         u32p, u32p, vp], c.c_int64),
         "dq_hip_region_skeleton": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp, u32p, u32p],
+                                   c.c_int64),
+        "dq_hip_region_contours_dev": ([c.c_int, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, c.c_uint64, vp, vp, vp,
+                                        vp, vp, vp], c.c_int64),
+        "dq_hip_region_contours": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, c.c_uint64, vp, vp, vp, vp, vp],
                                    c.c_int64),
         "dq_hip_quant_weighted_dev": ([c.c_int, vp, c.c_uint32, vp, u32p, vp, c.c_int, vp], c.c_int),
         "dq_hip_quant_weighted_regions_dev": ([c.c_int, c.c_int, vp, vp, vp, vp, vp, c.c_uint32, vp, c.c_int, vp],
@@ -1878,6 +1886,107 @@ def region_skeleton(regions2d, num_regions=None, max_iters=0):
     if r < 0:
         raise DivQuantError("dq_hip_region_skeleton: bad arguments")
     out["kept"], out["iterations"], out["converged"] = int(r), int(iterations.value), int(converged.value)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Contours of all regions of a region map (include/dq_hip.h, "region
+# contours"): OpenCV's border following of the outer border of the component
+# that holds a region's first pixel, a neighbour counting only when it has the
+# pixel's own id (the reference's findContourOutline on every region's mask).
+# Exact integers, independent of scheduling.  An id >= num_regions is background.
+CONTOUR_OUTPUTS = ("offsets", "points", "codes", "len", "visits")
+CONTOUR_LISTS = ("points", "codes")
+CONTOUR_MAX_REGIONS = 0xFFFFFFFF - 1024
+CONTOUR_NO_CODE = 8                    # the code of the one point of a contour of length 1
+
+
+class ContourOverflowError(DivQuantError):
+    """The contours of the map have 2^32 - 1 points or more (-2), or its border pixels more than
+    2^32 - 2 neighbours of their own id (-3)."""
+
+
+def _contour_shape(width, height, num_regions, orientation, point_capacity=None):
+    width, height, nreg = _distance_shape(width, height, num_regions, 0)
+    if nreg > CONTOUR_MAX_REGIONS:
+        raise ValueError("num_regions %d: at most 2^32 - 1025" % nreg)
+    if orientation not in (0, 1):
+        raise ValueError("orientation is 0 (as followed) or 1 (reversed), not %r" % (orientation,))
+    if point_capacity is not None:
+        point_capacity = int(point_capacity)
+        if not 0 <= point_capacity <= 0xFFFFFFFFFFFFFFFF:
+            raise ValueError("point_capacity %d is not a uint64" % point_capacity)
+    return width, height, nreg, point_capacity
+
+
+def _contour_shapes(w, h, nreg, cap):
+    """name -> (shape, numpy dtype, torch dtype name) of every output of the call."""
+    return {"offsets": ((nreg + 1,), np.uint32, "int32"), "points": ((cap,), np.uint32, "int32"),
+            "codes": ((cap,), np.uint8, "uint8"), "len": ((nreg,), np.uint32, "int32"),
+            "visits": ((h, w), np.uint8, "uint8")}
+
+
+def _contour_result(r, name):
+    if r in (-2, -3):
+        raise ContourOverflowError("%s: the contours do not fit 32-bit offsets (%d)" % (name, r))
+    if r < 0:
+        raise DivQuantError("%s: bad arguments" % name)
+    return int(r)
+
+
+def region_contours_device(t_regions, width, height, num_regions, orientation=0, outputs=None, point_capacity=None,
+                           device=0, stream=None):
+    """The contours of all regions of a device-resident width x height map of
+    region ids (contiguous, 4-byte elements; an id >= num_regions is
+    background).  orientation: 0 the points as border following emits them
+    (counter-clockwise on the screen, from the region's first pixel), 1 the
+    reference's reversed list.  outputs: the names wanted of CONTOUR_OUTPUTS
+    (None: all).  point_capacity: the entries of room in "points" and "codes";
+    None counts first and sizes them to M (two calls when a list is wanted).
+    Returns (M, out): the points of all contours and a dict of device tensors --
+    "offsets" (num_regions + 1,) and "len" (num_regions,) int32 storage of the
+    uint32 values, "points" Coord words x | y << 16 and "codes" uint8 (written
+    only when M <= their length), "visits" (height, width) uint8.  Synchronous.
+    ValueError for bad tensors, sizes or names (nothing runs)."""
+    width, height, nreg, cap = _contour_shape(width, height, num_regions, orientation, point_capacity)
+    _elems(t_regions, width * height, 4, "t_regions")
+    want = _distance_outputs(outputs, CONTOUR_OUTPUTS)
+    lists = [name for name in CONTOUR_LISTS if name in want]
+    if cap is not None and cap > 0 and not lists:
+        raise ValueError("point_capacity without the output \"points\" or \"codes\"")
+    import torch
+    fn, reg = lib().dq_hip_region_contours_dev, _dptr(t_regions)
+    if lists and cap is None:   # count, then fill
+        t_len = torch.empty(nreg, dtype=torch.int32, device=f"cuda:{device}")
+        cap = _contour_result(fn(device, reg, width, height, nreg, orientation, 0, None, None, None, _dptr(t_len), None,
+                                 _stream_ptr(stream)), "dq_hip_region_contours_dev")
+    shapes = _contour_shapes(width, height, nreg, cap or 0)
+    out = {name: torch.empty(shapes[name][0], dtype=getattr(torch, shapes[name][2]), device=f"cuda:{device}")
+           for name in want}
+    opt = lambda name: _dptr(out[name]) if name in out and out[name].numel() else None  # noqa: E731
+    r = fn(device, reg, width, height, nreg, orientation, cap if lists else 0, *[opt(name) for name in CONTOUR_OUTPUTS],
+           _stream_ptr(stream))
+    return _contour_result(r, "dq_hip_region_contours_dev"), out
+
+
+def region_contours(regions2d, num_regions=None, orientation=0):
+    """The same of a host (H, W) map of ids (integers of at most 4 bytes;
+    num_regions None takes regions2d.max() + 1).  Returns a dict of numpy arrays
+    ("offsets" (R + 1,), "len" (R,), "points" (M,) uint32; "codes" (M,) uint8;
+    "visits" (H, W) uint8) and the int "total" (M)."""
+    reg, nreg = _distance_map(regions2d, num_regions)
+    h, w = reg.shape
+    _contour_shape(w, h, nreg, orientation)
+    _require_gpu()
+    fn = lib().dq_hip_region_contours
+    count = np.zeros(nreg, np.uint32)
+    total = _contour_result(fn(_ptr(reg), w, h, nreg, orientation, 0, None, None, None, _ptr(count), None),
+                            "dq_hip_region_contours")
+    shapes = _contour_shapes(w, h, nreg, total)
+    out = {name: np.zeros(shapes[name][0], shapes[name][1]) for name in CONTOUR_OUTPUTS}
+    opt = lambda name: _ptr(out[name]) if out[name].size else None  # noqa: E731
+    r = fn(_ptr(reg), w, h, nreg, orientation, total, *[opt(name) for name in CONTOUR_OUTPUTS])
+    out["total"] = _contour_result(r, "dq_hip_region_contours")
     return out
 
 

@@ -1,5 +1,5 @@
 // dq_abi_regions.cpp -- the region-map pipeline of the C ABI (include/dq_hip.h):
-// regions, adjacency, merge, containment, distance and cores, skeletons, pixel lists,
+// regions, adjacency, merge, containment, distance and cores, skeletons, contours, pixel lists,
 // capture windows, window tags and votes, and the per-region / per-window quant over them.
 //
 // Every stage has the same shape.  Both of its entry points fill the stage's
@@ -23,6 +23,7 @@
 #include "dq_abi_util.h"
 #include "dq_adjacency.h"
 #include "dq_contain.h"
+#include "dq_contour.h"
 #include "dq_distance.h"
 #include "dq_merge.h"
 #include "dq_pixels.h"
@@ -338,6 +339,65 @@ int64_t run_on(hipStream_t st, dq::SkeletonArgs a, uint32_t* iterations, uint32_
   if (iterations) *iterations = last_deleting;
   if (converged) *converged = stable ? 1u : 0u;
   return (int64_t)kept;
+}
+
+// -------------------------------------------------------------------------
+// Contours of a region map (dq_contour.hip).
+bool args_ok(const dq::ContourArgs& a) {
+  if (!a.regions) return false;
+  if (a.width == 0 || a.height == 0 || a.width > 65535u || a.height > 65535u ||
+      (uint64_t)a.width * a.height > 0x7FFFFFFFull)
+    return false;
+  // (the scans walk the regions in chunks: the last chunk's indexes stay below 2^32)
+  if (a.nregions == 0 || a.nregions > 0xFFFFFFFFu - dq::kRegionChunk) return false;
+  if (a.orientation != 0 && a.orientation != 1) return false;
+  if (!a.offsets && !a.points && !a.codes && !a.len && !a.visits) return false;
+  if (a.point_cap > 0 && !a.points && !a.codes) return false;
+  return aligned({a.regions, a.offsets, a.points, a.len});
+}
+
+// How many pointer-jumping rounds go out before the next read-back.
+uint32_t contour_group(uint32_t rounds) { return rounds < 8 ? 4u : 8u; }
+
+// Enqueues the mark pass, the links, the rounds in groups, the lengths and the
+// emit pass on st with scratch owned by the call, waits, returns M.  Read-backs:
+// S (sizes the links), one word per round of a group (a round that found every
+// start's chain resolved ends the rounds) and M (-2; do the lists fit).
+int64_t run_on(hipStream_t st, dq::ContourArgs a) {
+  Staging s(st);
+  const size_t R = a.nregions;
+  if (!a.len) a.len = s.alloc<uint32_t>(R);
+  a.scratch = s.alloc_bytes(dq::contour_scratch_bytes(a.width, a.height, a.nregions));
+  dq::launch_contour_mark(a, st);
+  const uint32_t states = s.read_word(dq::contour_states_word(a));
+  if (states > dq::kContourMaxStates) {
+    s.finish();
+    return -3;
+  }
+  if (states) a.links = s.alloc_bytes(dq::contour_links_bytes(states));
+  dq::launch_contour_links(a, states, st);
+  uint32_t rounds = 0;
+  bool resolved = states == 0;
+  uint32_t todo[8];
+  // A chain of L states is resolved after ceil(log2(L)) rounds: at most kContourMaxRounds, the loop ends by itself.
+  while (!resolved && rounds < dq::kContourMaxRounds) {
+    const uint32_t from = rounds, group = contour_group(rounds);
+    for (; rounds < from + group && rounds < dq::kContourMaxRounds; ++rounds) dq::launch_contour_jump(a, states, rounds, st);
+    s.fetch(todo, dq::contour_round_words(a) + from, rounds - from);
+    s.sync();
+    for (uint32_t l = from; l < rounds; ++l) resolved = resolved || todo[l - from] == 0;
+  }
+  dq::launch_contour_lengths(a, states, rounds, st);
+  const uint32_t total = s.read_word(dq::contour_total_word(a));
+  if (total == 0xFFFFFFFFu) {   // (the saturated sum: only len is written)
+    s.finish();
+    return -2;
+  }
+  if (!a.offsets) a.offsets = s.alloc<uint32_t>(R + 1);
+  DQ_HIP(dq::launch_contour_emit(a, states, rounds, total <= a.point_cap && total != 0, st));
+  DQ_HIP(hipGetLastError());
+  s.finish();
+  return (int64_t)total;
 }
 
 // -------------------------------------------------------------------------
@@ -921,6 +981,45 @@ int64_t dq_hip_region_skeleton(const uint32_t* regions, uint32_t width, uint32_t
   s.download(skel_area, d.skel_area, R), s.download(thick, d.thick, R);
   s.sync();
   return kept;
+}
+
+int64_t dq_hip_region_contours_dev(int device, const uint32_t* d_regions, uint32_t width, uint32_t height,
+                                   uint32_t nregions, int orientation, uint64_t point_cap, uint32_t* d_offsets,
+                                   uint32_t* d_points, uint8_t* d_codes, uint32_t* d_len, uint8_t* d_visits,
+                                   void* stream) {
+  dq::ContourArgs a{};
+  a.regions = d_regions, a.width = width, a.height = height, a.nregions = nregions, a.orientation = orientation;
+  a.point_cap = point_cap, a.offsets = d_offsets, a.points = d_points, a.codes = d_codes, a.len = d_len;
+  a.visits = d_visits;
+  if (!args_ok(a)) return -1;
+  return run_on(engine_stream(device, stream), a);
+}
+
+int64_t dq_hip_region_contours(const uint32_t* regions, uint32_t width, uint32_t height, uint32_t nregions,
+                               int orientation, uint64_t point_cap, uint32_t* offsets, uint32_t* points,
+                               uint8_t* codes, uint32_t* len, uint8_t* visits) {
+  dq::ContourArgs h{};
+  h.regions = regions, h.width = width, h.height = height, h.nregions = nregions, h.orientation = orientation;
+  h.point_cap = point_cap, h.offsets = offsets, h.points = points, h.codes = codes, h.len = len, h.visits = visits;
+  if (!args_ok(h)) return -1;
+  hipStream_t st = host_stream();
+  Staging s(st);
+  const size_t n = (size_t)width * height, R = nregions;
+  const size_t cap = (size_t)std::min<uint64_t>(point_cap, 0xFFFFFFFFull);   // (M is a word)
+  dq::ContourArgs d = h;
+  d.regions = s.upload(regions, n);
+  d.offsets = s.twin(offsets, R + 1), d.points = s.twin(points, cap), d.codes = s.twin(codes, cap);
+  d.len = s.twin(len, R), d.visits = s.twin(visits, n);
+  const int64_t total = run_on(st, d);
+  // nothing but len at -2; the lists only when all M entries fit
+  if (total >= 0 || total == -2) s.download(len, d.len, R);
+  if (total >= 0) {
+    const size_t m = (uint64_t)total <= point_cap ? (size_t)total : 0;
+    s.download(offsets, d.offsets, R + 1), s.download(visits, d.visits, n);
+    s.download(points, d.points, m), s.download(codes, d.codes, m);
+  }
+  s.sync();
+  return total;
 }
 
 int dq_hip_regions_by_size_dev(int device, uint32_t nregions, const uint32_t* d_area, uint32_t* d_order,

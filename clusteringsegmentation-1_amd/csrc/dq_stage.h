@@ -1,7 +1,7 @@
 // dq_stage.h -- the device idioms the region-map stages share (dq_regions.hip,
 // dq_adjacency.hip, dq_merge.hip, dq_pixels.hip, dq_windows.hip, dq_wtags.hip,
-// dq_contain.hip, dq_distance.hip, dq_skeleton.hip): the workgroup and chunk sizes, runs of equal keys along a
-// wave, the workgroup's LDS slot cache and groups of equal ids in a wave.  Free
+// dq_contain.hip, dq_distance.hip, dq_skeleton.hip, dq_contour.hip): the workgroup and chunk sizes, runs of
+// equal keys along a wave, the workgroup's LDS slot cache and groups of equal ids in a wave.  Free
 // functions of a few lines each; beside it dq_scan.h (prefix sums) and
 // dq_table.h (the 64-bit hash table).
 // Included by .hip files only.

@@ -939,6 +939,84 @@ int64_t dq_hip_region_skeleton(const uint32_t *regions, uint32_t width, uint32_t
                                uint32_t *skeled, uint16_t *when, uint32_t *skel_area,
                                uint32_t *thick, uint32_t *iterations, uint32_t *converged);
 
+/* ---- region contours (region map -> the ordered border pixels of every region,
+ * by border following) ---------------------------------------------------------
+ * The first thing the reference's clockwiseScanForShapeBounds does with a
+ * visited region (ClusteringSegmentation.cpp:5856 -> clockwiseScanOfHullCoords,
+ * superpixels/OpenCVHull.cpp:280-360 -> findContourOutline, :69-274): it renders
+ * the region into a frame-sized mask, takes findContours(RETR_LIST,
+ * CHAIN_APPROX_NONE) of the mask inside a 1-pixel border of zeros, subtracts
+ * (1, 1) from every point and reverses the list (:329-337).  This entry does
+ * the same for ALL regions of an id map in one call.  The rules are OpenCV
+ * 3.1's border-following loop for an outer border, written out: ONE exact
+ * answer per region that does not depend on scheduling.
+ * Inputs.  d_regions: a width x height map of uint32 ids.  An id < nregions = R
+ * is a region; its pixels need not be connected.  An id >= R is background.
+ * on_r(q) = q lies in the frame and id(q) == r; outside the frame counts as off
+ * (the reference's border of zeros; coordinates are frame coordinates, i.e.
+ * after its - (1, 1)).
+ * Rules.
+ *   1 Directions, y down: 0 = E (1,0), 1 = NE (1,-1), 2 = N (0,-1),
+ *     3 = NW (-1,-1), 4 = W (-1,0), 5 = SW (-1,1), 6 = S (0,1), 7 = SE (1,1).
+ *   2 Start.  p0[r] = the pixel of r with the lowest raster index (its W, NW, N
+ *     and NE neighbours are off).  d0 = the first of E, SE, S, SW (0, 7, 6, 5)
+ *     whose neighbour is on: OpenCV's clockwise search from s = 4.  If none is
+ *     on, the contour is [p0], len = 1.
+ *   3 Step.  A state is (p, d): a pixel p of r and a direction d whose neighbour
+ *     p + delta[d] is on ("the pixel we came from").  step(p, d): s = the first
+ *     of d + 1, d + 2, ... (mod 8) with on_r(p + delta[s]); the step emits point
+ *     p with code s and goes to state (p + delta[s], (s + 4) & 7).
+ *   4 Contour.  step from (p0, d0) until it is the start state again; the points
+ *     emitted, in that order, are findContours' outer border of the 8-connected
+ *     component that holds p0: counter-clockwise on the screen, starting at p0.
+ *     A pixel can appear more than once (a one-pixel spur is walked out and
+ *     back).  len[r] = the number of points, 0 for an id with no pixel.  Only the
+ *     component of p0 is traced and only its outer border: holes and further
+ *     components of an id are not (the reference asserts there are none,
+ *     OpenCVHull.cpp:134-184).
+ *   5 Orientation.  0: the list as in rule 4.  1: the reference's reversal,
+ *     point'[i] = point[len - 1 - i], what clockwiseScanOfHullCoords hands on.
+ *     In both, code[i] = the direction from point i to point (i + 1) mod len;
+ *     code[i] = 8 when len == 1.
+ *   6 Outputs.  offsets[0 .. R]: the exclusive prefix sum of len, offsets[R] = M;
+ *     points[offsets[r] + i]: the Coord word x | y << 16; codes: u8 per point;
+ *     len[r]; visits[p]: u8 per pixel, how often p appears in its own region's
+ *     contour, 0 for background.
+ * Returns M, synchronous on return.  d_points and d_codes are written only when
+ * M <= point_cap; with point_cap = 0 and both NULL the call only counts (offsets,
+ * len and visits are still written).  -2, with only d_len written, when M does
+ * not fit below 2^32 - 1.  -3, with nothing written, when the border pixels of
+ * the map have more than 2^32 - 2 on neighbours in all (the states the call
+ * numbers; no map below 2^29 pixels has).  -1, before any device work, for: NULL
+ * d_regions; width or height 0 or above 65535; width * height above 2^31 - 1;
+ * nregions == 0 or above 2^32 - 1025; orientation not 0 or 1; a word pointer
+ * (d_regions, d_offsets, d_points, d_len) not 4-B aligned; every output NULL;
+ * point_cap > 0 with both list pointers NULL.  Every output pointer may be NULL;
+ * nothing behind an array's stated size is written; no output may overlap the map.
+ * Scratch, allocated and freed in stream order by the call (no engine state is
+ * touched: calls on two streams may overlap): 5 B per pixel (a neighbour byte
+ * and the number of the pixel's first state), 12 B per region, 4 B per 1024
+ * pixels or regions and 136 B; 16 B per state (two buffers of (next, distance)
+ * words; a state is an on neighbour of a border pixel, a region pixel with a
+ * 4-neighbour off: 2 to 3 per border pixel on a smooth map); plus 4 B per
+ * region for each of d_len and d_offsets that is NULL.
+ * Launches: 13 + one per pointer-jumping round; ceil(log2(the longest len - 1))
+ * rounds are needed and one more sees that none is, sent 4, 4, then 8 at a time
+ * (33 at most).  Read-backs: the states, one per group of rounds (4 B a round),
+ * and M. */
+int64_t dq_hip_region_contours_dev(int device, const uint32_t *d_regions, uint32_t width,
+                                   uint32_t height, uint32_t nregions, int orientation,
+                                   uint64_t point_cap, uint32_t *d_offsets /*R + 1*/,
+                                   uint32_t *d_points /*point_cap*/,
+                                   uint8_t *d_codes /*point_cap*/, uint32_t *d_len /*R*/,
+                                   uint8_t *d_visits /*W*H*/, void *stream);
+/* The same on host arrays, the current device: one upload of the map, the call
+ * above, one download of the arrays asked for.  Same returns. */
+int64_t dq_hip_region_contours(const uint32_t *regions, uint32_t width, uint32_t height,
+                               uint32_t nregions, int orientation, uint64_t point_cap,
+                               uint32_t *offsets, uint32_t *points, uint8_t *codes,
+                               uint32_t *len, uint8_t *visits);
+
 /* ---- BGR24 frames (OpenCV CV_8UC3: B, G, R bytes, `stride` bytes per row)
  * quant_recurse of device BGR24 frames without the packed conversion
  * (SURVEY 8f.3): with uniq = 1 and continuous rows (stride == 3*width) the
